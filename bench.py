@@ -13,6 +13,11 @@ then ONE all_gather (RCCL) of the ln_lkd values selects the best row -- no data-
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus 1 --force-dist      # one rank, but through torch.distributed / RCCL like N > 1
+
+A plain run sets up, warms up, times the steps and prints the result line (the roofline figures in it come from the
+timed launches themselves).  `--full` adds what takes runs of its own: the CPU baseline (oracle on the host cores) and
+the parity check of row 0 against it (exit code 5 on a mismatch).  `--dump-outputs DIR` writes what the timed call
+returned (`ln_lkd_all`, `hp_best`, `best_row`) as DIR/<name>.npy, float64.
 """
 import argparse
 import json
@@ -77,18 +82,21 @@ def cpu_baseline(cfg, n, d, kernel, X, f, g, hp_row, threads_to_try=(16, 64, 128
     (1) evaluation with element-wise preconditioner scaling + LAPACK dpotrf/dpotrs -- the best-practice CPU
         path, reported as `value` so the GPU/CPU ratio is not inflated by (2); at full size for cfg2 / cfg3, on a
         bounded sample extrapolated with N^3 for cfg5 (N = 68000 does not finish in the budget of a bench run).
-        Timed at every BLAS thread count of `threads_to_try` that the box has CPUs for; `value` is the BEST of
-        them (`cores` = its thread count), `threads_tried` keeps all of them;
+        Timed at every BLAS thread count of `threads_to_try` that this process has CPUs and BLAS threads for (the
+        CPUs it may run on, and the size its BLAS pools started with: OpenBLAS 0.3.28's dpotrf crashes when a pool
+        is grown beyond that); `value` is the BEST of them (`cores` = its thread count), `threads_tried` keeps all;
     (2) the reference as written (five dense diag-matrix GEMMs, Kernel.py:224-252) on a bounded sample at the
         best thread count, extrapolated with N^3.
     Returns (record, oracle result of the full-size evaluation or None)."""
     from oracle import gp_oracle as orc
     try:
-        from threadpoolctl import threadpool_limits
+        from threadpoolctl import threadpool_info, threadpool_limits
     except Exception:  # pragma: no cover
-        threadpool_limits = None
+        threadpool_info = threadpool_limits = None
     noisy = cfg == "cfg5"
-    ncpu = os.cpu_count() or 1
+    ncpu = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    if threadpool_info is not None:
+        ncpu = min([ncpu] + [p["num_threads"] for p in threadpool_info() if p.get("user_api") == "blas"])
     tries = sorted({min(t, ncpu) for t in threads_to_try})
 
     def one(ns, as_written=False, reps=1):
@@ -235,7 +243,12 @@ def main():
     ap.add_argument("--factor-mode", default="auto", choices=["auto", "blocked", "tile64", "tile128"],
                     help="Cholesky schedule (include/gpgrad.h gpg_factor_mode); default: one dataflow launch")
     ap.add_argument("--batch", type=int, default=-1, help="restart rows per batched launch on small matrices (gpg_set_batch)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline (oracle on the host cores) and the "
+                         "parity check of row 0 against it")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline and the parity check out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed call returned as DIR/<name>.npy (float64)")
     ap.add_argument("--prof-all", action="store_true", help="time every kernel category (adds event overhead)")
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise torch.distributed even for one rank: the N > 1 code path (RCCL init, sharded selection, "
@@ -340,10 +353,14 @@ def main():
     barrier()
     t0 = time.perf_counter()
     # the product's own sharded selection: local block on this device, then the single collective + nanargmax
-    _, ln_all, best = multistart.select_best_restart(table_for(args.steps), timed_eval, group=group,
-                                                     device=coll_dev if use_dist else None)
+    hp_best, ln_all, best = multistart.select_best_restart(table_for(args.steps), timed_eval, group=group,
+                                                           device=coll_dev if use_dist else None)
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:                          # what select_best_restart handed back (every rank holds the same)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in (("ln_lkd_all", ln_all), ("hp_best", hp_best), ("best_row", [best])):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.asarray(arr, dtype=np.float64))
     collective_ms = multistart.last_collective_s * 1e3 if use_dist else 0.0
     dom_kernel = DOM_KERNELS[GP.last_factor()[0]]                # what the library actually launched
     prof = GP.prof_read()
@@ -392,7 +409,7 @@ def main():
         }
         if args.prof_all:
             result["kernel_ms_per_eval"] = {c: prof[c]["ms"] / args.steps for c in prof}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cb, r = cpu_baseline(args.config, n, d, kernel, X, f, g, hp_table[0])
             result["cpu_baseline"] = cb
             if r is not None and args.steps >= 1:

@@ -7,4 +7,4 @@ for cfg in "18048 5 10" "18048 1" "2560 5 64" "4608 5 16" "9216 1" "9216 5 8"; d
   echo -n "new pair: "; GPG_PAIR=1 timeout -k 10 60 ./tile_probe $cfg /dev/null || exit 1
 done
 cd $GRAFT_REPO_ROOT
-GPG_PAIR=0 timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 | python3 -c "import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print({k:d.get(k) for k in ('value','parity_ln_lkd_rel_err_row0','factor_fallbacks')}, d['roofline']['achieved'], d['cpu_baseline']['threads_tried'])"
+GPG_PAIR=0 timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 | python3 -c "import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print({k:d.get(k) for k in ('value','parity_ln_lkd_rel_err_row0','factor_fallbacks')}, d['roofline']['achieved'], d['cpu_baseline']['threads_tried'])"
