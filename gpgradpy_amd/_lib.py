@@ -22,7 +22,7 @@ ABI_SYMBOLS = (
     "gpg_create", "gpg_destroy", "gpg_last_error", "gpg_set_grad_mask", "gpg_set_data", "gpg_lkd", "gpg_lkd_grad", "gpg_lkd_batch", "gpg_lkd_grad_batch",
     "gpg_setup_eval", "gpg_predict", "gpg_predict_grad", "gpg_predict_var", "gpg_predict_hess", "gpg_get_matrix", "gpg_kern_rtensor", "gpg_kern_rtensor_grad_hp", "gpg_kern_rtensor_hess_x", "gpg_factor_apply", "gpg_dcov_quadform", "gpg_cond_fro", "gpg_set_noise", "gpg_abs_rowsum", "gpg_set_gradient_nugget", "gpg_lkd_alpha", "gpg_prof_enable", "gpg_prof_read", "gpg_set_panel", "gpg_set_lookahead", "gpg_set_factor_mode", "gpg_set_pair_mode", "gpg_factor_fallbacks", "gpg_overlap_fallbacks", "gpg_solve_fallbacks", "gpg_last_factor", "gpg_set_batch", "gpg_reserve_batch", "gpg_set_max_workgroups",
     "gpg_device_info", "gpg_multi_create", "gpg_multi_destroy", "gpg_multi_last_error", "gpg_multi_count", "gpg_multi_set_data",
-    "gpg_multi_lkd_batch",
+    "gpg_multi_lkd_batch", "gpg_set_mean_order", "gpg_lkd_beta", "gpg_setup_eval_mean", "gpg_multi_set_mean_order",
 )
 
 
@@ -75,6 +75,14 @@ def load():
     lib.gpg_lkd_grad_batch.restype = C.c_int
     lib.gpg_setup_eval.argtypes = [vp, C.POINTER(GpgHp), C.c_double, dp]
     lib.gpg_setup_eval.restype = C.c_int
+    lib.gpg_setup_eval_mean.argtypes = [vp, C.POINTER(GpgHp), dp, dp]
+    lib.gpg_setup_eval_mean.restype = C.c_int
+    lib.gpg_set_mean_order.argtypes = [vp, C.c_int]
+    lib.gpg_set_mean_order.restype = C.c_int
+    lib.gpg_lkd_beta.argtypes = [vp, dp]
+    lib.gpg_lkd_beta.restype = C.c_int
+    lib.gpg_multi_set_mean_order.argtypes = [vp, C.c_int]
+    lib.gpg_multi_set_mean_order.restype = C.c_int
     lib.gpg_predict.argtypes = [vp, C.c_int, dp, C.c_double, dp, dp, dp]
     lib.gpg_predict.restype = C.c_int
     lib.gpg_predict_grad.argtypes = [vp, C.c_int, dp, C.c_double, dp, dp, dp, dp, dp]

@@ -125,10 +125,12 @@ static int ensure_scal(gpg_ctx* c, int slots) {
     c->h_scal = nullptr; c->h_info = nullptr;
   }
   c->scal = nullptr; c->info = nullptr; c->scal_slots = 0;
-  GPG_HIP_OK(c, hipMalloc(&c->scal, sizeof(double) * 8 * slots));
+  c->betav = nullptr;
+  GPG_HIP_OK(c, hipMalloc(&c->scal, sizeof(double) * (8 + GPG_BETA_STRIDE) * slots));   // scalars [8 x slots] | coefficient vectors
+  c->betav = c->scal + (size_t)8 * slots;
   GPG_HIP_OK(c, hipMalloc(&c->info, sizeof(int) * slots));
   if (!keep_host) {
-    GPG_HIP_OK(c, hipHostMalloc(&c->h_scal, sizeof(double) * 8 * slots));
+    GPG_HIP_OK(c, hipHostMalloc(&c->h_scal, sizeof(double) * (8 + GPG_BETA_STRIDE) * slots));
     GPG_HIP_OK(c, hipHostMalloc(&c->h_info, sizeof(int) * slots));
   }
   c->scal_slots = slots;
@@ -266,7 +268,7 @@ void gpg_destroy(gpg_ctx* c) {
   ws_park(c);
   double* bufs[] = {c->ws[0].A, c->ws[0].dvec, c->ws[0].invp, c->ws[0].zvec, c->ws[0].tmpv, c->ws[0].dinv,
                     c->ws[1].A, c->ws[1].dvec, c->ws[1].invp, c->ws[1].zvec, c->ws[1].tmpv, c->ws[1].dinv,
-                    c->Xt, c->y, c->noise, c->scal, c->Wt, c->xq_dev,
+                    c->Xt, c->y, c->noise, c->scal, c->eval_beta_dev, c->Wt, c->xq_dev,
                     c->musig, c->gradbuf, c->dense_tmp, c->Wfull, c->Minv, c->gpartial, c->batchA, c->batchV, c->vec_rows, c->vec_x, c->apply_buf,
                     c->batchW, c->batchM, c->batchZ, c->gres, c->Kbuf, c->Tbuf};
   for (double* b : bufs) if (b) (void)hipFree(b);
@@ -391,6 +393,17 @@ static int solve_failure(gpg_ctx* c) {
   return -4;
 }
 
+// coefficient vector of slot 0 behind the scalars of the pinned block (first-order mean only: the constant is scal[1])
+static hipError_t fetch_beta(gpg_ctx* c) {
+  return hipMemcpyAsync(c->h_scal + (size_t)8 * c->scal_slots, c->betav, sizeof(double) * c->n_beta, hipMemcpyDeviceToHost, c->stream);
+}
+static void keep_beta(gpg_ctx* c, const gpg_lkd_out* out) {
+  c->last_beta_valid = out->info == 0;
+  if (!c->last_beta_valid) return;
+  if (c->n_beta > 1) for (int i = 0; i < c->n_beta; ++i) c->last_beta[i] = c->h_scal[(size_t)8 * c->scal_slots + i];
+  else c->last_beta[0] = out->beta;
+}
+
 static int gpg_lkd_once(gpg_ctx* c, const gpg_hp* hp, gpg_lkd_out* out) {
   int rc = check_hp(c, hp);
   if (rc) return rc;
@@ -398,8 +411,10 @@ static int gpg_lkd_once(gpg_ctx* c, const gpg_hp* hp, gpg_lkd_out* out) {
   GPG_HIP_OK(c, hipSetDevice(c->device));
   GPG_WS(c, 0);
   c->zero_info_in_prep = true;                             // one launch fewer than a memset of the info word
+  c->last_beta_valid = false;
   enqueue_lkd(c, hp, 0);
   GPG_HIP_OK(c, hipMemcpyAsync(c->h_scal, c->scal, sizeof(double) * 8, hipMemcpyDeviceToHost, c->stream));
+  if (c->n_beta > 1) GPG_HIP_OK(c, fetch_beta(c));
   GPG_HIP_OK(c, hipStreamSynchronize(c->stream));
   GPG_HIP_OK(c, hipGetLastError());
   GPG_LAUNCH_OK(c);
@@ -407,6 +422,7 @@ static int gpg_lkd_once(gpg_ctx* c, const gpg_hp* hp, gpg_lkd_out* out) {
   if (internal_failure(c, c->h_info, 1)) return -4;
   c->factor_valid = (c->h_info[0] == 0);
   finish_lkd(c, hp, c->h_scal, c->h_info[0], out);
+  keep_beta(c, out);
   return out->info;
 }
 
@@ -427,10 +443,12 @@ static int gpg_lkd_grad_once(gpg_ctx* c, const gpg_hp* hp, gpg_lkd_out* out, dou
   c->zero_info_in_prep = true;
   // small matrix on the dataflow schedule: W = L^-T goes to the second stream right behind the factorisation (cholesky_dataflow.hip)
   const bool overlap = c->Npad <= 32768 && gpg_overlap_inverse_begin(c, 1);
+  c->last_beta_valid = false;
   enqueue_lkd(c, hp, 0);                                   // factor + beta + r'K^-1 r + ln det (scal slot 0)
   c->chol_flags_override = nullptr;                        // (consumed by the 64-tile launch; cleared in case another schedule ran)
   if (overlap && !gpg_overlap_inverse_trinv(c, 1, c->A, 0, c->dinv, 0, c->Wfull, c->info)) { c->err = "overlapped inverse: launch refused"; return -2; }
   GPG_HIP_OK(c, hipMemcpyAsync(c->h_scal, c->scal, sizeof(double) * 8, hipMemcpyDeviceToHost, c->stream));
+  if (c->n_beta > 1) GPG_HIP_OK(c, fetch_beta(c));
   // Large matrices: look at the factorisation's info before spending two more N^3/3 sweeps on a failed factor.  Small ones
   // (the sweeps cost less than a host round trip is worth): everything is enqueued at once and judged at the end; the kernels
   // run to completion on whatever a failed factorisation left behind (their waits depend on flags, not on values).
@@ -476,6 +494,7 @@ static int gpg_lkd_grad_once(gpg_ctx* c, const gpg_hp* hp, gpg_lkd_out* out, dou
   g_aa[c->d + 3] = g_inv[c->d + 3] = 0.0;                  // hp_kernel slot: RatQu only
   for (int k = 0; k < ns; ++k) { g_aa[k] = h[k]; g_inv[k] = h[ns + k]; }
   c->alpha_valid = true;
+  keep_beta(c, out);
   return 0;
 }
 
@@ -537,6 +556,7 @@ static int gpg_lkd_batch_once(gpg_ctx* c, int m, const double* hp_rows, int row_
   GPG_HIP_OK(c, hipSetDevice(c->device));
   GPG_WS(c, 0);
   c->alpha_valid = false;                                  // the vectors of set 0 are redirected / rewritten by the groups
+  c->last_beta_valid = false;
   int rc = ensure_scal(c, m);
   if (rc) return rc;
   if (m > c->items_cap) {
@@ -632,6 +652,7 @@ static int gpg_lkd_grad_batch_once(gpg_ctx* c, int m, const double* hp_rows, int
   GPG_HIP_OK(c, hipSetDevice(c->device));
   GPG_WS(c, 0);
   c->alpha_valid = false;                                  // the vectors of set 0 are redirected / rewritten by the groups
+  c->last_beta_valid = false;
   int rc = ensure_scal(c, m);
   if (rc) return rc;
   if (m > c->items_cap) {
@@ -767,6 +788,10 @@ static int gpg_lkd_grad_batch_once(gpg_ctx* c, int m, const double* hp_rows, int
   GPG_HIP_OK(c, hipGetLastError());
   GPG_LAUNCH_OK(c);
   if (internal_failure(c, c->h_info, m)) return -4;
+  // the device word holds what the factorisation and the solves report; a singular GLS system of the first-order mean
+  // (info = N + 1 + pivot) is known to the reduction alone, which passes it along in scal[7]
+  for (int i = 0; i < m; ++i)
+    if (c->h_info[i] == 0) c->h_info[i] = (int)c->h_scal[(size_t)8 * i + 7];
   for (int i = 0; i < m; ++i) {
     finish_lkd(c, &hps[i], c->h_scal + (size_t)8 * i, c->h_info[i], &out[i]);
     double* ga = g_aa + (size_t)i * (c->d + 4);
@@ -780,17 +805,25 @@ static int gpg_lkd_grad_batch_once(gpg_ctx* c, int m, const double* hp_rows, int
   return 0;
 }
 
-static int gpg_setup_eval_once(gpg_ctx* c, const gpg_hp* hp, double beta, double* alpha_out) {
+// betav != nullptr (host [n_beta], first-order mean): the coefficient vector; otherwise the constant beta
+static int gpg_setup_eval_once(gpg_ctx* c, const gpg_hp* hp, double beta, const double* betav, double* alpha_out) {
   int rc = check_hp(c, hp);
   if (rc) return rc;
   GPG_HIP_OK(c, hipSetDevice(c->device));
   GPG_WS(c, 1);                                   // the posterior's own factor storage (GpEvalModel.py:17-57)
   c->eval_ready = false;
+  if (betav) {
+    if (!c->eval_beta_dev) GPG_HIP_OK(c, hipMalloc(&c->eval_beta_dev, sizeof(double) * GPG_BETA_STRIDE));
+    GPG_HIP_OK(c, hipStreamSynchronize(c->stream));             // (a predict of the previous posterior may still read the vector)
+    GPG_HIP_OK(c, hipMemcpy(c->eval_beta_dev, betav, sizeof(double) * c->n_beta, hipMemcpyHostToDevice));
+    beta = betav[0];
+  }
   AsmParams p = make_params(c, hp, 0);
   c->last_precon = p.precon;
   c->prep_valid = true;
   c->last_factor_ws = 1;
   GPG_HIP_OK(c, hipMemsetAsync(c->info, 0, sizeof(int), c->stream));
+  c->prep_beta = betav ? c->eval_beta_dev : nullptr;                          // consumed by the launch that follows
   gpg_launch_prep(c, p, hp->var_fval, hp->var_fgrad, -beta, 1.0, 0.0, 0.0);   // RHS row 0 = (y - V beta) P^-1
   gpg_launch_assembly(c, p);
   gpg_cholesky(c);
@@ -813,6 +846,7 @@ static int gpg_setup_eval_once(gpg_ctx* c, const gpg_hp* hp, double beta, double
   if (solve_failure(c)) return -4;
   c->eval_ready = true;
   c->eval_beta = beta;
+  c->eval_linear = betav != nullptr;
   c->eval_params = p;   // theta etc. for the cross kernel
   c->err.clear();
   return 0;
@@ -877,7 +911,36 @@ int gpg_lkd_grad_batch(gpg_ctx* c, int m, const double* hp_rows, int row_len, do
   return with_fallback(c, [&] { return gpg_lkd_grad_batch_once(c, m, hp_rows, row_len, eta, wellcond, closed_form_varK, out, g_aa, g_inv); });
 }
 int gpg_setup_eval(gpg_ctx* c, const gpg_hp* hp, double beta, double* alpha_out) {
-  return with_fallback(c, [&] { return gpg_setup_eval_once(c, hp, beta, alpha_out); });
+  if (c && c->mean_order != 0) { c->err = "gpg_setup_eval takes a scalar beta: with mean order 1 call gpg_setup_eval_mean (beta [dim + 1])"; return -1; }
+  return with_fallback(c, [&] { return gpg_setup_eval_once(c, hp, beta, nullptr, alpha_out); });
+}
+int gpg_setup_eval_mean(gpg_ctx* c, const gpg_hp* hp, const double* beta, double* alpha_out) {
+  if (!c) return -1;
+  if (!beta) { c->err = "beta is NULL"; return -1; }
+  if (c->mean_order == 0) return with_fallback(c, [&] { return gpg_setup_eval_once(c, hp, beta[0], nullptr, alpha_out); });
+  return with_fallback(c, [&] { return gpg_setup_eval_once(c, hp, 0.0, beta, alpha_out); });
+}
+
+int gpg_set_mean_order(gpg_ctx* c, int order) {
+  if (!c) return -1;
+  if (order != 0 && order != 1) { c->err = "mean order must be 0 (constant) or 1 (first-order polynomial)"; return -1; }
+  GPG_HIP_OK(c, hipSetDevice(c->device));
+  GPG_HIP_OK(c, hipStreamSynchronize(c->stream));
+  c->mean_order = order;
+  c->n_beta = order == 1 ? c->d + 1 : 1;
+  c->prep_beta = nullptr;
+  c->alpha_valid = c->last_beta_valid = false;
+  c->factor_valid = c->eval_ready = c->prep_valid = false;
+  c->ws[0].factor_valid = c->ws[1].factor_valid = c->ws[0].prep_valid = c->ws[1].prep_valid = false;
+  return 0;
+}
+
+int gpg_lkd_beta(gpg_ctx* c, double* beta) {
+  if (!c) return -1;
+  if (!beta) { c->err = "beta is NULL"; return -1; }
+  if (!c->last_beta_valid) { c->err = "no coefficients: gpg_lkd / gpg_lkd_grad must succeed first (no batched call in between)"; return -1; }
+  for (int i = 0; i < c->n_beta; ++i) beta[i] = c->last_beta[i];
+  return 0;
 }
 int gpg_factor_fallbacks(gpg_ctx* c) { return c ? c->factor_fallbacks : -1; }
 int gpg_overlap_fallbacks(gpg_ctx* c) { return c ? c->overlap_fallbacks : -1; }

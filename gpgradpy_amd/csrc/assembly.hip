@@ -48,10 +48,15 @@ __global__ void prep_diag_kernel(AsmParams P, const double* __restrict__ noise, 
 }
 
 // rows [N, ld) of every column: identity padding and the right-hand-side rows
-//   rhs row 0 = (s0 V + t0 y) P^-1, rhs row 1 = (s1 V + t1 y) P^-1, V = [1_n; 0] (GpMeanFun.py:172-191)
+//   nb == 1 (constant mean): rhs row 0 = (s0 V + t0 y) P^-1, rhs row 1 = (s1 V + t1 y) P^-1, V = [1_n; 0] (GpMeanFun.py:172-191)
+//   nb == d + 1 (first-order mean): V = calc_aug_vand -- value row a: [1, x_a], gradient row (i, a): e_(i+1); masked points have no
+//     gradient rows, so the column of V a gradient row belongs to follows from its block alone.
+//       betav == nullptr: rhs rows 0 .. nb - 1 = the columns of V P^-1, rhs row nb = y P^-1
+//       betav != nullptr: rhs row 0 = (y - V beta) P^-1 (posterior set-up)
 __global__ void prep_rows_kernel(AsmParams P, const double* __restrict__ y, const double* __restrict__ invp,
                                  double s0, double t0, double s1, double t1, double* __restrict__ A,
-                                 const gpg_batch_item* __restrict__ items, size_t v_stride, size_t a_stride) {
+                                 const gpg_batch_item* __restrict__ items, size_t v_stride, size_t a_stride,
+                                 int nb, const double* __restrict__ Xt, const double* __restrict__ betav) {
   if (items) {
     const int bz = blockIdx.y;
     P = items[bz].p;
@@ -65,9 +70,25 @@ __global__ void prep_rows_kernel(AsmParams P, const double* __restrict__ y, cons
       v = (r == c) ? 1.0 : 0.0;
     } else if (c < P.N) {
       int j = r - P.Npad;
-      double vc = c < P.n ? 1.0 : 0.0;
-      if (j == 0) v = (s0 * vc + t0 * y[c]) * invp[c];
-      else if (j == 1) v = (s1 * vc + t1 * y[c]) * invp[c];
+      if (nb == 1) {
+        double vc = c < P.n ? 1.0 : 0.0;
+        if (j == 0) v = (s0 * vc + t0 * y[c]) * invp[c];
+        else if (j == 1) v = (s1 * vc + t1 * y[c]) * invp[c];
+      } else if (betav == nullptr) {
+        if (j < nb) {
+          double vc;
+          if (c < P.n) vc = j == 0 ? 1.0 : Xt[(size_t)(j - 1) * P.n + c];
+          else vc = (c - P.n) / P.ng + 1 == j ? 1.0 : 0.0;
+          v = vc * invp[c];
+        } else if (j == nb) v = y[c] * invp[c];
+      } else if (j == 0) {
+        double m;
+        if (c < P.n) {
+          m = betav[0];
+          for (int k = 1; k < nb; ++k) m += betav[k] * Xt[(size_t)(k - 1) * P.n + c];
+        } else m = betav[(c - P.n) / P.ng + 1];
+        v = (y[c] - m) * invp[c];
+      }
     }
     A[col + r] = v;
   }
@@ -391,7 +412,8 @@ void gpg_launch_prep(gpg_ctx* c, const AsmParams& p, double var_fval, double var
   hipLaunchKernelGGL(prep_diag_kernel, dim3((p.Npad + 255) / 256), dim3(256), 0, c->stream, p, c->noise, var_fval,
                      var_fgrad, c->dvec, c->invp, (const gpg_batch_item*)nullptr, (size_t)0, zero_info);
   hipLaunchKernelGGL(prep_rows_kernel, dim3(p.Npad), dim3(256), 0, c->stream, p, c->y, c->invp, s0, t0, s1, t1, c->A,
-                     (const gpg_batch_item*)nullptr, (size_t)0, (size_t)0);
+                     (const gpg_batch_item*)nullptr, (size_t)0, (size_t)0, c->n_beta, c->Xt, c->prep_beta);
+  c->prep_beta = nullptr;
 }
 
 void gpg_launch_assembly(gpg_ctx* c, const AsmParams& p) {
@@ -405,14 +427,14 @@ void gpg_launch_assembly(gpg_ctx* c, const AsmParams& p) {
 
 // The three launches above for B matrices at once: c->dvec / c->invp / c->A are the buffers of matrix 0, matrix b
 // sits b * v_stride / b * a_stride behind them, items[b] (device) carries its parameters; p = the parameters of any
-// of them (shape only).  rhs rows as for a likelihood evaluation: row 0 = V P^-1, row 1 = y P^-1.
+// of them (shape only).  rhs rows as for a likelihood evaluation: rows 0 .. n_beta - 1 = V P^-1, row n_beta = y P^-1.
 void gpg_launch_prep_assembly_batch(gpg_ctx* c, const AsmParams& p, int B, const gpg_batch_item* items, size_t v_stride,
                                     size_t a_stride) {
   c->alpha_valid = false;
   hipLaunchKernelGGL(prep_diag_kernel, dim3((p.Npad + 255) / 256, B), dim3(256), 0, c->stream, p, c->noise, 0.0, 0.0, c->dvec,
                      c->invp, items, v_stride, (int*)nullptr);
   hipLaunchKernelGGL(prep_rows_kernel, dim3(p.Npad, B), dim3(256), 0, c->stream, p, c->y, c->invp, 1.0, 0.0, 0.0, 1.0, c->A,
-                     items, v_stride, a_stride);
+                     items, v_stride, a_stride, c->n_beta, c->Xt, (const double*)nullptr);
   double bytes = 8.0 * (double)p.N * ((double)p.N + 1.0) / 2.0 * B;
   gpg_prof_begin(c, GPG_PROF_ASSEMBLY, bytes);
   if (p.kernel == GPG_KERNEL_SQEXP) launch_assemble_d<GPG_KERNEL_SQEXP>(c, p, B, items, v_stride, a_stride);

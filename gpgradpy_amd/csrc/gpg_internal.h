@@ -12,6 +12,8 @@
 #define GPG_NBI 64        // inner (diagonal block) width of the panel factorisation
 #define GPG_INFO_INTERNAL 0x7fffffff   // info value: dataflow factorisation aborted (dependency wait timed out)
 #define GPG_RHS_ROWS 128  // right-hand-side rows appended below the matrix (ride along the Cholesky)
+#define GPG_MAX_NBETA (GPG_MAX_DIM + 1)   // coefficients of the first-order mean: n_beta + 1 <= 18 right-hand-side rows are in use
+#define GPG_BETA_STRIDE 24                // doubles per slot of the coefficient vectors behind the reduction scalars
 
 // Arguments of the fused assembly kernels (passed by value -> SGPRs / kernarg segment).
 struct AsmParams {
@@ -111,7 +113,10 @@ struct gpg_ctx {
   double* zvec = nullptr;    // [Npad] L^-T L^-1 P^-1 (y - V beta)  (= p * alpha)
   double* tmpv = nullptr;    // [Npad] scratch for the backward solve
   double* dinv = nullptr;    // [Npad] reciprocal pivots 1 / L_jj of the factor in A
-  double* scal = nullptr;    // device scalars of the reductions
+  double* scal = nullptr;    // device scalars of the reductions: [8 x scal_slots], then betav
+  double* betav = nullptr;   // [GPG_BETA_STRIDE x scal_slots] GLS coefficients per slot (first-order mean), inside the scal allocation
+  double* eval_beta_dev = nullptr;   // [GPG_BETA_STRIDE] coefficients of the posterior kept by gpg_setup_eval_mean (on first use)
+  const double* prep_beta = nullptr; // consumed by the next gpg_launch_prep: RHS row 0 = (y - V beta) P^-1 with this device vector
   int* info = nullptr;       // device: first failing pivot (0 = none)
   double* vec_rows = nullptr;   // [64 x vec_rows_cols] carrier tile of the single-vector backward solve (on first use)
   int vec_rows_cols = 0;        // = Npad of the full-gradient shape (allocation size)
@@ -156,6 +161,11 @@ struct gpg_ctx {
   int last_factor_ws = 0;      // set of the most recent factorisation (gpg_factor_apply, gpg_get_matrix 3, gpg_dcov_quadform)
   bool eval_ready = false;     // set 1 holds factor + alpha of a successful gpg_setup_eval
   double eval_beta = 0.0;
+  int mean_order = 0;          // 0: constant mean, 1: first-order polynomial (gpg_set_mean_order)
+  int n_beta = 1;              // 1 or d + 1: RHS rows 0 .. n_beta - 1 hold V P^-1, row n_beta holds y P^-1
+  bool eval_linear = false;    // the kept posterior has a first-order mean (eval_beta_dev)
+  double last_beta[GPG_MAX_NBETA] = {0};   // coefficients of the most recent successful gpg_lkd / gpg_lkd_grad
+  bool last_beta_valid = false;
   int last_precon = 0;         // wellcond of the matrix currently in A
   int scal_slots = 0;
   AsmParams eval_params;       // hyperparameters of the factor kept for gpg_predict
@@ -206,7 +216,7 @@ void gpg_forward_rows(gpg_ctx* c, double* W, int ldw, int rows, int valid = -1);
 void gpg_launch_lkd_reduce(gpg_ctx* c, int slot);                        // writes scal[slot*8 ..]
 void gpg_backward_solve(gpg_ctx* c);                                     // zvec <- L^-T (RHS row 0)
 void gpg_launch_alpha(gpg_ctx* c, double* alpha_dev);                    // alpha = zvec * invp
-void gpg_launch_predict_reduce(gpg_ctx* c, int nx, int nxp, double beta, double varK, int phase);
+void gpg_launch_predict_reduce(gpg_ctx* c, int nx, int nxp, double beta, double varK, int phase);   // eval_linear: mean from eval_beta_dev
 void gpg_backward_rows(gpg_ctx* c, double* Z, int ldz, int nrhs, double* tbuf);  // Z <- Z L^-1 (multi-RHS)
 void gpg_launch_cross_grad(gpg_ctx* c, const AsmParams& p, int nx, int nxp, double* g1, double* g2);
 void gpg_launch_hess_stage(gpg_ctx* c, const AsmParams& p, int nxp, double* h1, double* h2, double* T, int stage);

@@ -28,12 +28,20 @@ __device__ __forceinline__ double wave_sum_g(double v) {
   return v;
 }
 
-// RHS row 0 <- RHS row 1 - beta * RHS row 0  ( = L^-1 P^-1 (y - V beta) ), beta from the reduction scalars
-__global__ void combine_rows_kernel(double* __restrict__ A, int ld, int Npad, const double* __restrict__ scal) {
+// RHS row 0 <- RHS row 1 - beta * RHS row 0  ( = L^-1 P^-1 (y - V beta) ), beta from the reduction scalars;
+// first-order mean (nb = d + 1 > 1): RHS row 0 <- w_y - sum_i beta_i w_i with w_i = RHS row i, w_y = RHS row nb, beta from betav
+__global__ void combine_rows_kernel(double* __restrict__ A, int ld, int Npad, const double* __restrict__ scal, int nb,
+                                    const double* __restrict__ betav) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= Npad) return;
-  const double beta = scal[1];
   double* col = A + (size_t)c * ld + Npad;
+  if (nb > 1) {
+    double t = col[nb];
+    for (int i = 0; i < nb; ++i) t -= betav[i] * col[i];
+    col[0] = t;
+    return;
+  }
+  const double beta = scal[1];
   col[0] = col[1] - beta * col[0];
 }
 
@@ -365,7 +373,7 @@ void launch_contract_d(gpg_ctx* c, const AsmParams& p, double* partial, dim3 gri
 
 void gpg_launch_combine_rows(gpg_ctx* c, int slot) {
   hipLaunchKernelGGL(combine_rows_kernel, dim3((c->Npad + 255) / 256), dim3(256), 0, c->stream, c->A, c->ld, c->Npad,
-                     c->scal + (size_t)slot * 8);
+                     c->scal + (size_t)slot * 8, c->n_beta, c->betav + (size_t)slot * GPG_BETA_STRIDE);
 }
 
 void gpg_launch_identity(gpg_ctx* c, double* W, int ldw) {

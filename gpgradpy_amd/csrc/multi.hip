@@ -60,6 +60,15 @@ int gpg_multi_set_data(gpg_multi* m, const double* x, const double* data_vec, co
   return 0;
 }
 
+int gpg_multi_set_mean_order(gpg_multi* m, int order) {
+  if (!m) return -1;
+  for (size_t i = 0; i < m->ctx.size(); ++i) {
+    const int rc = gpg_set_mean_order(m->ctx[i], order);
+    if (rc != 0) { m->err = std::string("device ") + std::to_string(m->device[i]) + ": " + gpg_last_error(m->ctx[i]); return rc; }
+  }
+  return 0;
+}
+
 int gpg_multi_lkd_batch(gpg_multi* m, int nrows, const double* hp_rows, int row_len, double eta, int wellcond,
                         int closed_form_varK, gpg_lkd_out* out, int* best) {
   if (!m) return -1;

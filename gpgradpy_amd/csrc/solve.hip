@@ -1,6 +1,7 @@
 // Reductions and triangular sweeps around the factorisation (gfx950).
 //   lkd_reduce      : ln det, GLS mean beta, r' K^-1 r from the diagonal of L and the two RHS rows
 //                     (reference GpMeanFun.py:102-108, CalcLkd.py:153-168 / 220-226) -- wave-reduced
+//   lkd_reduce_lin  : the same for the first-order mean: Gram matrix of the d + 2 RHS rows, (d+1) x (d+1) GLS solve
 //   backward solve  : z = L^-T w for the single vector needed by alpha (GpEvalModel.py:57)
 //   predict_reduce  : mu = beta + Kyx' alpha, sig2 = 1 - diag(Kxy K^-1 Kyx) (GpEvalModel.py:162-168)
 //   extract         : dense N x N copies on request (tests / drop-in 7-tuple)
@@ -32,6 +33,13 @@ __device__ void block_sum(double (&v)[NV], double* sh /* [NV * 16] */) {
     v[q] = s;
   }
   __syncthreads();
+}
+
+// orders the LDS accesses of ONE wave across a step of a wave-local algorithm (no workgroup barrier: the other waves are not involved)
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // scal[0] = ln_det, [1] = beta, [2] = r'K^-1 r, [3] = V'K^-1 V, [4] = V'K^-1 y, [7] = the factorisation's info word (so that the
@@ -67,6 +75,127 @@ __global__ void __launch_bounds__(1024) lkd_reduce_kernel(const double* __restri
     scal[3] = v[2];
     scal[4] = v[3];
     scal[7] = (double)info[blockIdx.x];
+  }
+}
+
+// The same reduction for the first-order mean (V = calc_aug_vand, nb = d + 1 columns; GpMeanFun.py:69-122): the forward-solved
+// right-hand-side rows w_0 .. w_(nb-1) (= L^-1 P^-1 V) and w_nb (= L^-1 P^-1 y) sit below the factor, nr = nb + 1 <= 18 contiguous
+// doubles per matrix column.  One workgroup per matrix (batched launches as lkd_reduce_kernel):
+//   pass 1  column chunks of kLinChunk columns x nr rows are staged in LDS (row stride kLinChunk + 1: the rows a wave reads at one
+//           column sit in different banks, equal addresses are broadcast); thread (pair, slice) owns ONE entry (i, j), i <= j, of the
+//           nr x nr Gram matrix of the rows over the columns = slice (mod kLinSlices) -- (d+2)(d+3)/2 <= 171 pairs x 4 slices, one
+//           accumulator per thread; the slices are added in slice order.  G = W W' is its leading nb x nb block, b = W w_y its last
+//           column.  The two log-det sums as in lkd_reduce_kernel.
+//   solve   G = C C' by wave 0 alone (lane <-> row, wave-local ordering, no workgroup barrier), beta = C^-T C^-1 b by its lane 0.  A pivot that is not above kLinPivTol times the
+//           diagonal entry it started from reports info = N + 1 + pivot: V has no full column rank in the K^-1 inner product.
+//   pass 2  r'K^-1 r = sum_c (w_y - sum_i beta_i w_i)^2, the explicit residual (y'K^-1 y - b'G^-1 b cancels).
+// Every sum has a fixed order: the result is reproducible and the same for a single and a batched launch.
+// scal as lkd_reduce_kernel ([1] = beta_0, [3] = G_00, [4] = b_0); betav [nb] = the coefficients (NaN on a singular G).
+constexpr int kLinChunk = 256, kLinSlices = 4, kLinRowsMax = GPG_MAX_NBETA + 1;
+constexpr double kLinPivTol = 1e-12;
+__global__ void __launch_bounds__(1024) lkd_reduce_lin_kernel(const double* __restrict__ A, int ld, int N, int Npad, int nb,
+                                                              const double* __restrict__ dvec, int precon,
+                                                              double* __restrict__ scal, double* __restrict__ betav,
+                                                              size_t v_stride, size_t a_stride, const int* __restrict__ info) {
+  A += blockIdx.x * a_stride; dvec += blockIdx.x * v_stride; scal += blockIdx.x * 8; betav += (size_t)blockIdx.x * GPG_BETA_STRIDE;
+  __shared__ double sh[4 * 16];
+  __shared__ double rows[kLinRowsMax][kLinChunk + 1];
+  __shared__ double part[kLinSlices][256];
+  __shared__ double G[GPG_MAX_NBETA][GPG_MAX_NBETA + 1];
+  __shared__ double bsh[GPG_MAX_NBETA], beta_sh[GPG_MAX_NBETA], diag0[GPG_MAX_NBETA];
+  __shared__ int sing;
+  const int nr = nb + 1, npair = nr * (nr + 1) / 2;
+  const int tid = threadIdx.x, pr = tid & 255, sl = tid >> 8;
+  // pair index -> (pi, pj), pi <= pj, column by column of the upper triangle
+  int pi = 0, pj = 0;
+  if (pr < npair) {
+    int q = pr;
+    while (q > pj) { q -= pj + 1; ++pj; }
+    pi = q;
+  }
+  if (tid == 0) sing = 0;
+  double v[2] = {0.0, 0.0};
+  for (int c = tid; c < N; c += blockDim.x) {
+    v[0] += log(A[(size_t)c * ld + c]);
+    if (precon) v[1] += 0.5 * log(dvec[c]);
+  }
+  double acc = 0.0;
+  for (int c0 = 0; c0 < N; c0 += kLinChunk) {
+    const int cn = min(kLinChunk, N - c0);
+    __syncthreads();
+    for (int t = tid; t < cn * nr; t += blockDim.x) {
+      const int cc = t / nr, r = t - cc * nr;
+      rows[r][cc] = A[(size_t)(c0 + cc) * ld + Npad + r];
+    }
+    __syncthreads();
+    if (pr < npair)
+      for (int cc = sl; cc < cn; cc += kLinSlices) acc += rows[pi][cc] * rows[pj][cc];
+  }
+  part[sl][pr] = acc;
+  block_sum<2>(v, sh);                                   // (its barriers also order part[][])
+  if (sl == 0 && pr < npair) {
+    double s = part[0][pr];
+    for (int q = 1; q < kLinSlices; ++q) s += part[q][pr];
+    if (pj < nb) { G[pj][pi] = s; G[pi][pj] = s; }
+    else if (pi < nb) bsh[pi] = s;
+  }
+  __syncthreads();
+  const double g00 = G[0][0], b0 = bsh[0];
+  // G = C C', lower triangle in place, and the two substitutions: wave 0 alone (lane <-> row, nb <= 17 < 64), the other fifteen
+  // waves go straight to the barrier below.  Inside one wave the LDS operations complete in program order; wave_lds_sync keeps
+  // the compiler from moving them across the steps.  `s` is uniform over the wave: every lane reads the same pivot.
+  if (tid < 64) {
+    if (tid < nb) diag0[tid] = G[tid][tid];
+    int s = 0;
+    for (int k = 0; k < nb; ++k) {
+      wave_lds_sync();
+      const double piv = G[k][k];
+      if (!(piv > kLinPivTol * diag0[k])) { s = k + 1; break; }
+      const double ckk = sqrt(piv);
+      wave_lds_sync();                                    // every lane has read the pivot before lane k overwrites it
+      if (tid > k && tid < nb) G[tid][k] = G[tid][k] / ckk;
+      if (tid == k) G[k][k] = ckk;
+      wave_lds_sync();
+      if (tid > k && tid < nb)
+        for (int j = k + 1; j <= tid; ++j) G[tid][j] -= G[tid][k] * G[j][k];
+    }
+    wave_lds_sync();
+    if (tid == 0) {
+      sing = s;
+      if (s != 0) {
+        for (int i = 0; i < nb; ++i) beta_sh[i] = __longlong_as_double(0x7ff8000000000000LL);
+      } else {
+        for (int i = 0; i < nb; ++i) {                    // C z = b
+          double t = bsh[i];
+          for (int j = 0; j < i; ++j) t -= G[i][j] * beta_sh[j];
+          beta_sh[i] = t / G[i][i];
+        }
+        for (int i = nb - 1; i >= 0; --i) {               // C' beta = z
+          double t = beta_sh[i];
+          for (int j = i + 1; j < nb; ++j) t -= G[j][i] * beta_sh[j];
+          beta_sh[i] = t / G[i][i];
+        }
+      }
+    }
+  }
+  __syncthreads();
+  double rr[1] = {0.0};
+  for (int c = tid; c < N; c += blockDim.x) {
+    const double* w = A + (size_t)c * ld + Npad;
+    double t = w[nb];
+    for (int i = 0; i < nb; ++i) t -= beta_sh[i] * w[i];
+    rr[0] += t * t;
+  }
+  block_sum<1>(rr, sh);
+  if (tid < nb) betav[tid] = beta_sh[tid];
+  if (tid == 0) {
+    const int finfo = info[blockIdx.x];
+    scal[0] = 2.0 * (v[0] + v[1]);
+    scal[1] = beta_sh[0];
+    scal[2] = rr[0];
+    scal[3] = g00;
+    scal[4] = b0;
+    scal[7] = (double)(finfo != 0 ? finfo : (sing != 0 ? N + sing : 0));
   }
 }
 
@@ -123,10 +252,21 @@ __device__ __forceinline__ void kb_add(double& s, double& comp, double x) {
   s = t;
 }
 
-// phase 0: out[j] = beta + sum_c Wt[j, c] z[c] ; phase 1: out[j] = 1 - sum_c Wt[j, c]^2
+// prior mean at query j: the constant beta, or with a first-order mean (betav != nullptr, device [d + 1]; Xq [d x nxp])
+// beta_0 + xq_j . beta_1..d (GpMeanFun.py:14-67)
+__device__ __forceinline__ double prior_mean(double beta, const double* __restrict__ betav, const double* __restrict__ Xq, int d, int nxp,
+                                             int j) {
+  if (betav == nullptr) return beta;
+  double m = betav[0];
+  for (int k = 0; k < d; ++k) m += betav[k + 1] * Xq[(size_t)k * nxp + j];
+  return m;
+}
+
+// phase 0: out[j] = mean_j + sum_c Wt[j, c] z[c] ; phase 1: out[j] = 1 - sum_c Wt[j, c]^2
 __global__ void __launch_bounds__(1024) predict_reduce_kernel(const double* __restrict__ Wt, int nxp, int N,
                                                               const double* __restrict__ z, double beta, int phase,
-                                                              double* __restrict__ out) {
+                                                              double* __restrict__ out, const double* __restrict__ betav,
+                                                              const double* __restrict__ Xq, int d) {
   __shared__ double sh[16][64];
   const int jl = threadIdx.x & 63, cg = threadIdx.x >> 6;
   const int j = blockIdx.x * 64 + jl;
@@ -142,7 +282,7 @@ __global__ void __launch_bounds__(1024) predict_reduce_kernel(const double* __re
     double s = 0.0, cs = 0.0;
     for (int q = 0; q < 16; ++q) kb_add(s, cs, sh[q][jl]);
     s += cs;
-    out[j] = phase == 0 ? beta + s : 1.0 - s;
+    out[j] = phase == 0 ? prior_mean(beta, betav, Xq, d, nxp, j) + s : 1.0 - s;
   }
 }
 
@@ -172,7 +312,8 @@ __global__ void __launch_bounds__(1024) predict_partial_kernel(const double* __r
 }
 
 __global__ void __launch_bounds__(1024) predict_final_kernel(const double* __restrict__ partial, int nxp, int S, double beta,
-                                                             int phase, double* __restrict__ out) {
+                                                             int phase, double* __restrict__ out, const double* __restrict__ betav,
+                                                             const double* __restrict__ Xq, int d) {
   __shared__ double sh[16][64];
   const int jl = threadIdx.x & 63, cg = threadIdx.x >> 6;
   const int j = blockIdx.x * 64 + jl;
@@ -184,7 +325,7 @@ __global__ void __launch_bounds__(1024) predict_final_kernel(const double* __res
     double s = 0.0, cs = 0.0;
     for (int q = 0; q < 16; ++q) kb_add(s, cs, sh[q][jl]);
     s += cs;
-    out[j] = phase == 0 ? beta + s : 1.0 - s;
+    out[j] = phase == 0 ? prior_mean(beta, betav, Xq, d, nxp, j) + s : 1.0 - s;
   }
 }
 
@@ -237,7 +378,7 @@ __global__ void __launch_bounds__(256) cross_grad_kernel(AsmParams P, const doub
                                                          const double* __restrict__ Xq, int nxp,
                                                          const double* __restrict__ invp, const double* __restrict__ zvec,
                                                          const double* __restrict__ Z, double* __restrict__ g1o,
-                                                         double* __restrict__ g2o) {
+                                                         double* __restrict__ g2o, const double* __restrict__ betav) {
   __shared__ double sh[2 * D * 16];
   const int q = blockIdx.x, n = P.n, ng = P.ng;
   const int nblk = P.use_grad ? D + 1 : 1;
@@ -310,7 +451,8 @@ __global__ void __launch_bounds__(256) cross_grad_kernel(AsmParams P, const doub
   }
   block_sum<2 * D>(g, sh);
   if (threadIdx.x < D) {
-    g1o[(size_t)q * D + threadIdx.x] = g[threadIdx.x];
+    // first-order mean: its gradient beta_1..d is the same at every query (GpMeanFun.py:14-67)
+    g1o[(size_t)q * D + threadIdx.x] = betav ? g[threadIdx.x] + betav[threadIdx.x + 1] : g[threadIdx.x];
     g2o[(size_t)q * D + threadIdx.x] = g[D + threadIdx.x];
   }
 }
@@ -320,7 +462,7 @@ void launch_cross_grad_d(gpg_ctx* c, const AsmParams& p, int nx, int nxp, double
 #define CASE_D(DD)                                                                                          \
   case DD:                                                                                                  \
     hipLaunchKernelGGL((cross_grad_kernel<KERN, DD>), dim3(nx), dim3(256), 0, c->stream, p, c->Xt, c->xq_dev, nxp, \
-                       c->invp, c->zvec, c->Wt, g1, g2);                                                    \
+                       c->invp, c->zvec, c->Wt, g1, g2, c->eval_linear ? c->eval_beta_dev : (const double*)nullptr); \
     break;
   switch (p.d) {
     CASE_D(1) CASE_D(2) CASE_D(3) CASE_D(4) CASE_D(5) CASE_D(6) CASE_D(7) CASE_D(8)
@@ -541,15 +683,23 @@ __global__ void extract_kernel(const double* __restrict__ A, int ld, int N, cons
 
 void gpg_launch_lkd_reduce(gpg_ctx* c, int slot) {
   gpg_prof_begin(c, GPG_PROF_REDUCE, 0.0);
-  hipLaunchKernelGGL(lkd_reduce_kernel, dim3(1), dim3(1024), 0, c->stream, c->A, c->ld, c->N, c->Npad, c->dvec,
-                     c->last_precon, c->scal + (size_t)slot * 8, (size_t)0, (size_t)0, c->info);   // c->info: this evaluation's word
+  if (c->n_beta > 1)
+    hipLaunchKernelGGL(lkd_reduce_lin_kernel, dim3(1), dim3(1024), 0, c->stream, c->A, c->ld, c->N, c->Npad, c->n_beta, c->dvec,
+                       c->last_precon, c->scal + (size_t)slot * 8, c->betav + (size_t)slot * GPG_BETA_STRIDE, (size_t)0, (size_t)0, c->info);
+  else
+    hipLaunchKernelGGL(lkd_reduce_kernel, dim3(1), dim3(1024), 0, c->stream, c->A, c->ld, c->N, c->Npad, c->dvec,
+                       c->last_precon, c->scal + (size_t)slot * 8, (size_t)0, (size_t)0, c->info);   // c->info: this evaluation's word
   gpg_prof_end(c);
 }
 
 void gpg_launch_lkd_reduce_batch(gpg_ctx* c, int slot0, int B, size_t v_stride, size_t a_stride, const int* info0) {
   gpg_prof_begin(c, GPG_PROF_REDUCE, 0.0);
-  hipLaunchKernelGGL(lkd_reduce_kernel, dim3(B), dim3(1024), 0, c->stream, c->A, c->ld, c->N, c->Npad, c->dvec,
-                     c->last_precon, c->scal + (size_t)slot0 * 8, v_stride, a_stride, info0);
+  if (c->n_beta > 1)
+    hipLaunchKernelGGL(lkd_reduce_lin_kernel, dim3(B), dim3(1024), 0, c->stream, c->A, c->ld, c->N, c->Npad, c->n_beta, c->dvec,
+                       c->last_precon, c->scal + (size_t)slot0 * 8, c->betav + (size_t)slot0 * GPG_BETA_STRIDE, v_stride, a_stride, info0);
+  else
+    hipLaunchKernelGGL(lkd_reduce_kernel, dim3(B), dim3(1024), 0, c->stream, c->A, c->ld, c->N, c->Npad, c->dvec,
+                       c->last_precon, c->scal + (size_t)slot0 * 8, v_stride, a_stride, info0);
   gpg_prof_end(c);
 }
 
@@ -682,17 +832,18 @@ void gpg_launch_alpha(gpg_ctx* c, double* alpha_dev) {
 
 void gpg_launch_predict_reduce(gpg_ctx* c, int nx, int nxp, double beta, double varK, int phase) {
   (void)nx; (void)varK;
+  const double* bv = c->eval_linear ? c->eval_beta_dev : nullptr;
   const int S = std::min(128, c->Npad / nxp);      // slices; the partial sums live in tmpv [Npad]
   if (S >= 2) {
     const int chunk = (c->N + S - 1) / S;
     hipLaunchKernelGGL(predict_partial_kernel, dim3(nxp / 64, S), dim3(1024), 0, c->stream, c->Wt, nxp, c->N, chunk, c->zvec,
                        phase, c->tmpv);
     hipLaunchKernelGGL(predict_final_kernel, dim3(nxp / 64), dim3(1024), 0, c->stream, c->tmpv, nxp, S, beta, phase,
-                       c->musig + (size_t)phase * nxp);
+                       c->musig + (size_t)phase * nxp, bv, c->xq_dev, c->d);
     return;
   }
   hipLaunchKernelGGL(predict_reduce_kernel, dim3(nxp / 64), dim3(1024), 0, c->stream, c->Wt, nxp, c->N, c->zvec, beta,
-                     phase, c->musig + (size_t)phase * nxp);
+                     phase, c->musig + (size_t)phase * nxp, bv, c->xq_dev, c->d);
 }
 
 void gpg_launch_extract(gpg_ctx* c, int which) {

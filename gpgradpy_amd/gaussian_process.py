@@ -118,11 +118,13 @@ class GaussianProcess(HparaOptz):
             self.hp_kernel_range = None
         self.kernel_has_hp = self.hp_kernel_default is not None                 # Kernel.py:111-112
         self.hp_kernel = self.hp_kernel_default
-        if mean_fun_type != 'poly_ord_0':
+        # 'poly_ord_1': first-order trend (universal kriging).  The reference carries its algebra (calc_vand / calc_aug_vand /
+        # calc_model_max_lkd_poly / eval_mean_fun_poly, GpMeanFun.py:14-191) and only set_mean_fun_op stops short of it.
+        if mean_fun_type not in ('poly_ord_0', 'poly_ord_1'):
             raise Exception(f'mean_fun_type = {mean_fun_type} not available')     # GpMeanFun.py:203-204
         self.mean_fun_type = mean_fun_type
-        self.n_beta_coeff = 1
-        self.beta_var_npara = 1
+        self.n_beta_coeff = dim + 1 if mean_fun_type == 'poly_ord_1' else 1
+        self.beta_var_npara = self.n_beta_coeff
         self.device = int(device)
         self._lib = _lib.load()
         self._ctx = None
@@ -468,6 +470,9 @@ class GaussianProcess(HparaOptz):
             if rc != 0:
                 raise _lib.GpgError(f'gpg_create failed ({rc}): {self._lib.gpg_last_error(None).decode()}')
             self._ctx, self._ctx_shape = ctx, shape
+            rc = self._lib.gpg_set_mean_order(self._ctx, 1 if self.n_beta_coeff > 1 else 0)
+            if rc != 0:
+                raise _lib.GpgError(f'gpg_set_mean_order failed ({rc}): {self._err()}')
         if self.use_grad:
             mask = None if self.bvec_use_grad is None else np.ascontiguousarray(self.bvec_use_grad, dtype=np.uint8)
             rc = self._lib.gpg_set_grad_mask(self._ctx, None if mask is None else mask.ctypes.data_as(C.POINTER(C.c_ubyte)))
@@ -944,6 +949,12 @@ class GaussianProcess(HparaOptz):
                         ev, evec = np.linalg.eigh(Kc)
                         cond_grad_fail = self._cond_grad_from_vectors(hp, cond_fail, ev[0], evec[:, -1], evec[:, 0])
             return LkdInfo(cond=cond_fail, cond_grad=cond_grad_fail), False
+        hp_beta = np.array([out.beta])
+        if self.n_beta_coeff > 1:
+            hp_beta = np.empty(self.n_beta_coeff)
+            rcb = self._lib.gpg_lkd_beta(self._ctx, _lib.as_dp(hp_beta))
+            if rcb != 0:
+                raise _lib.GpgError(f'gpg_lkd_beta failed ({rcb}): {self._err()}')
         hp_beta_grad = None
         if calc_grad and (noisy or not lkd_use_adj_mtd) and not self._skip_beta_grad:
             # GpMeanFun.py:109-120 (the noisy path always passes K_grad_hp: CalcLkd.py:216-217); needs the state the gradient call
@@ -990,7 +1001,7 @@ class GaussianProcess(HparaOptz):
                 ln_det_grad = self._slots_to_hp(-2.0 * g_inv) if calc_lkd else None
                 if not noisy:
                     hp_varK_grad = self._slots_to_hp(-g_aa / self.n_data)
-        info = LkdInfo(hp_beta=np.array([out.beta]), hp_beta_grad=hp_beta_grad, hp_varK=None if noisy else out.varK,
+        info = LkdInfo(hp_beta=hp_beta, hp_beta_grad=hp_beta_grad, hp_varK=None if noisy else out.varK,
                        hp_varK_grad=hp_varK_grad, ln_det_Kmat=out.ln_det if calc_lkd or not noisy else None,
                        ln_det_Kmat_grad=ln_det_grad, ln_lkd=ln_lkd if calc_lkd else None, ln_lkd_grad=ln_lkd_grad,
                        data_vec=self._data_vec if noisy else None, cond=cond, cond_grad=cond_grad)
@@ -1015,10 +1026,11 @@ class GaussianProcess(HparaOptz):
         return out
 
     def _beta_grad_device(self, hp, hp_vals, varK_mat):
-        """hp_beta_grad [1, n_hp] of calc_model_max_lkd_poly (GpMeanFun.py:109-120): beta_grad_k = term1 G_k term2 with
+        """hp_beta_grad [n_beta_coeff, n_hp] of calc_model_max_lkd_poly (GpMeanFun.py:109-120): beta_grad_k = term1 G_k term2 with
         term1 = (V' K^-1 V)^-1 (K^-1 V)' =: u' and term2 = K^-1 V beta - K^-1 y = -alpha, i.e. -u' G_k alpha -- the polarisation of
         the device's quadratic form v' G_k v (gpg_dcov_quadform) at u + alpha and u - alpha; K^-1 V through the factor on the
-        device (gpg_factor_apply), alpha from gpg_lkd_alpha.  Right after the gpg_lkd_grad call of calc_lkd_all."""
+        device (gpg_factor_apply), alpha from gpg_lkd_alpha.  With a first-order mean u has one column per coefficient,
+        K^-1 V (V' K^-1 V)^-1, and the polarisation runs once per column.  Right after the gpg_lkd_grad call of calc_lkd_all."""
         N, n = self.n_data, self.n_eval
         alpha = np.empty(N)
         rc = self._lib.gpg_lkd_alpha(self._ctx, _lib.as_dp(alpha))
@@ -1029,20 +1041,41 @@ class GaussianProcess(HparaOptz):
             kd = np.ones(N)
             kd[n:] = np.kron(self.theta2gamma(np.asarray(hp_vals.theta, dtype=float)) ** 2, np.ones(self.n_grad))
             pvec = np.sqrt(kd + self.calc_noise_vec(hp_vals) / varK_mat)
-        V = np.zeros(N)
-        V[:n] = 1.0
+        V = self._aug_vand()
+        KinvV = np.empty_like(V)
         w = np.empty(N)
-        rc = self._lib.gpg_factor_apply(self._ctx, 1, _lib.as_dp(np.ascontiguousarray(V / pvec)), _lib.as_dp(w))
-        if rc != 0:
-            raise _lib.GpgError(f'gpg_factor_apply failed ({rc}): {self._err()}')
-        KinvV = w / pvec
-        u = KinvV / (V @ KinvV)
-        q = np.zeros((2, self.dim + 4))
-        for i, v in enumerate((u + alpha, u - alpha)):
-            rc = self._lib.gpg_dcov_quadform(self._ctx, C.byref(hp), _lib.as_dp(np.ascontiguousarray(v)), _lib.as_dp(q[i]))
+        for j in range(V.shape[1]):
+            rc = self._lib.gpg_factor_apply(self._ctx, 1, _lib.as_dp(np.ascontiguousarray(V[:, j] / pvec)), _lib.as_dp(w))
             if rc != 0:
-                raise _lib.GpgError(f'gpg_dcov_quadform failed ({rc}): {self._err()}')
-        return -self._slots_to_hp((q[0] - q[1]) / 4.0)[None, :]
+                raise _lib.GpgError(f'gpg_factor_apply failed ({rc}): {self._err()}')
+            KinvV[:, j] = w / pvec
+        if V.shape[1] == 1:
+            U = KinvV / (V[:, 0] @ KinvV[:, 0])
+        else:
+            U = np.linalg.solve(V.T @ KinvV, KinvV.T).T                          # term1' of GpMeanFun.py:103
+        rows = []
+        for j in range(V.shape[1]):
+            u = U[:, j]
+            q = np.zeros((2, self.dim + 4))
+            for i, v in enumerate((u + alpha, u - alpha)):
+                rc = self._lib.gpg_dcov_quadform(self._ctx, C.byref(hp), _lib.as_dp(np.ascontiguousarray(v)), _lib.as_dp(q[i]))
+                if rc != 0:
+                    raise _lib.GpgError(f'gpg_dcov_quadform failed ({rc}): {self._err()}')
+            rows.append(-self._slots_to_hp((q[0] - q[1]) / 4.0))
+        return np.array(rows)
+
+    def _aug_vand(self):
+        """calc_aug_vand (GpMeanFun.py:172-191) of the data the device holds: [N, n_beta_coeff]; value row a: [1, x_a] (x scaled
+        as get_scl_x_w_dist gives it), gradient row (i, a): e_(i+1), rows of masked points left out."""
+        N, n, d = self.n_data, self.n_eval, self.dim
+        V = np.zeros((N, self.n_beta_coeff))
+        V[:n, 0] = 1.0
+        if self.n_beta_coeff > 1:
+            V[:n, 1:] = self.get_scl_x_w_dist(want_tensor=False)[0]
+            if self.use_grad:
+                for i in range(d):
+                    V[n + i * self.n_grad:n + (i + 1) * self.n_grad, i + 1] = 1.0
+        return V
 
     def calc_lkd_varK_pnlt(self, varK, fval_vec):
         # CalcLkd.py:118-133 (noise-free path only, as in the reference: CalcLkd.py:204 leaves the noisy path out)
@@ -1166,10 +1199,12 @@ class GaussianProcess(HparaOptz):
         """GpEvalModel.py:17-57: factor kept on the device, alpha = K^-1 (y - V beta) returned to the host."""
         self._hp_vals_model_setup = copy.copy(self.hp_vals)
         hp, keep = self._make_hp(self.hp_vals, 1.0, closed_form=not self.b_has_noisy_data)   # b_normlz_w_varK=True
-        beta = float(np.ravel(self.hp_vals.beta)[0])
+        beta = np.ascontiguousarray(np.ravel(self.hp_vals.beta), dtype=np.float64)
+        assert beta.size == self.n_beta_coeff, \
+            f'Size of beta_vec is {beta.size} but n_basis = {self.n_beta_coeff}'           # GpMeanFun.py:45
         alpha = np.empty(self.n_data)
         t0 = time.time()
-        rc = self._lib.gpg_setup_eval(self._ctx, C.byref(hp), beta, _lib.as_dp(alpha))
+        rc = self._lib.gpg_setup_eval_mean(self._ctx, C.byref(hp), _lib.as_dp(beta), _lib.as_dp(alpha))
         self._time_chofac += time.time() - t0
         if rc < 0:
             raise _lib.GpgError(f'gpg_setup_eval failed ({rc}): {self._err()}')

@@ -168,7 +168,7 @@ class HparaOptz:
                 return
             all_data = np.load(file2load, allow_pickle=False)
         name = self.surr_name
-        idx = all_data[name + 'hp_beta_all'].size                                # n_beta_coeff = 1: one entry per iteration
+        idx = all_data[name + 'hp_beta_all'].shape[0]                            # [iterations, n_beta_coeff]
         for k in self._history_names():
             getattr(self, k)[:idx] = all_data[name + k]
 

@@ -53,7 +53,7 @@ typedef struct {
 typedef struct {
   double ln_lkd;  /* marginal log-likelihood, without the N ln(2 pi) constant (CalcLkd.py:168,226) */
   double ln_det;  /* 2 sum log diag(P L)                               (CalcLkd.py:165,225)       */
-  double beta;    /* GLS constant mean                                  (GpMeanFun.py:103-107)     */
+  double beta;    /* GLS constant mean; beta[0] with mean order 1       (GpMeanFun.py:103-107)     */
   double varK;    /* closed-form varK, or varK_mat on the noisy path    (CalcLkd.py:159)           */
   double rKr;     /* r' Kcov^-1 r with r = y - V beta                   (CalcLkd.py:154,221)       */
   int info;       /* 0, or first non-positive pivot (1-based)                                      */
@@ -85,6 +85,27 @@ int gpg_set_data(gpg_ctx* ctx, const double* x, const double* data_vec, const do
  * (Kernel.py:140-143, 207-208, 218).  Likelihood-side state is invalidated; a posterior set up by gpg_setup_eval keeps its factor. */
 int gpg_set_noise(gpg_ctx* ctx, const double* noise_var);
 
+/* Mean function (GpMeanFun.py).
+ *   0 (default): constant mean, V = [1_n; 0] (GpMeanFun.py:160-163).
+ *   1: first-order polynomial ('poly_ord_1', universal kriging), n_beta = dim + 1, V = calc_aug_vand (GpMeanFun.py:172-191):
+ *      value row a: [1, x_a]; gradient row (i, a): e_(i+1) (points masked by gpg_set_grad_mask have no gradient rows).
+ * x is the x given to gpg_set_data (with a data-rescaling method the caller passes the scaled x, as the reference uses
+ * get_scl_x_w_dist).  The dim + 1 columns of V P^-1 and y P^-1 ride through every factorisation schedule as right-hand-side
+ * rows (dim + 2 <= 18 of the 128), so L^-1 P^-1 [V, y] costs no extra N^3 work; the (dim+1) x (dim+1) GLS system
+ * (calc_model_max_lkd_poly, GpMeanFun.py:69-122) is formed, factorised and solved by one workgroup per matrix on the device.
+ * Invalidates likelihood- and posterior-side state; callable before or after gpg_set_data.  With order 1:
+ *   - gpg_lkd, gpg_lkd_grad, gpg_lkd_batch, gpg_lkd_grad_batch, gpg_multi_lkd_batch and gpg_lkd_alpha use the GLS optimum beta
+ *     [n_beta]; gpg_lkd_out.beta is beta[0] (gpg_lkd_beta gives the vector).  The adjoint gradient formulas are unchanged
+ *     (V' alpha = 0 still holds).  A singular V' Kcov^-1 V (no gradients and fewer than dim + 1 points, or points that are not
+ *     affinely independent) gives info = N + 1 + j, j the 0-based pivot of the small system, and NaN results.  The call then
+ *     counts as a failed factorisation in every respect: although the Cholesky factor of the matrix itself is good, the context
+ *     marks it invalid (gpg_get_matrix 3 and gpg_factor_apply refuse until the next successful call).
+ *   - gpg_predict* add the mean and its gradient: mu += beta_0 + xq . beta_1..d, dmudx += beta_1..d; d2mudx2 is unchanged (the
+ *     Hessian of the mean is zero).  sig, dsigdx, d2sigdx2 and gpg_predict_var are unchanged: as in the reference, the posterior
+ *     variance does NOT include the uncertainty of the mean coefficients.
+ *   - gpg_get_matrix, gpg_factor_apply, gpg_dcov_quadform, gpg_cond_fro, gpg_abs_rowsum and gpg_kern_* do not depend on the mean. */
+int gpg_set_mean_order(gpg_ctx* ctx, int order);
+
 /* Likelihood ------------------------------------------------------------------------------------- */
 
 /* Replaces CalcLkd.calc_lkd_all(hp, calc_lkd=True, calc_cond=False, calc_grad=False)
@@ -113,6 +134,10 @@ int gpg_lkd_grad(gpg_ctx* ctx, const gpg_hp* hp, gpg_lkd_out* out, double* g_aa,
 int gpg_lkd_batch(gpg_ctx* ctx, int m, const double* hp_rows, int row_len, double eta, int wellcond,
                   int closed_form_varK, gpg_lkd_out* out);
 
+/* beta [n_beta] (1 or dim + 1 entries, gpg_set_mean_order) of the most recent successful gpg_lkd / gpg_lkd_grad on this context
+ * (no batched call in between); gpg_lkd_out.beta stays beta[0].  Replaces LkdInfo.hp_beta (CalcLkd.py:14-26). */
+int gpg_lkd_beta(gpg_ctx* ctx, double* beta);
+
 /* Value AND adjoint gradient of m restart rows in one call: what m SLSQP runs of the reference's multi-start
  * (OptzLkd.py:249-290, one calc_store_likelihood per iterate: OptzLkd.py:15-100) ask for when they advance in lock step.
  * Rows as gpg_lkd_batch; out [m]; g_aa, g_inv [m, dim + 4] row-major with the slots of gpg_lkd_grad.  Rows whose
@@ -136,6 +161,7 @@ void gpg_multi_destroy(gpg_multi* m);
 const char* gpg_multi_last_error(const gpg_multi* m); /* m may be NULL: error of the last failed create */
 int gpg_multi_count(const gpg_multi* m);
 int gpg_multi_set_data(gpg_multi* m, const double* x, const double* data_vec, const double* noise_var);
+int gpg_multi_set_mean_order(gpg_multi* m, int order);   /* gpg_set_mean_order on every context */
 int gpg_multi_lkd_batch(gpg_multi* m, int nrows, const double* hp_rows, int row_len, double eta, int wellcond,
                         int closed_form_varK, gpg_lkd_out* out, int* best);
 
@@ -149,6 +175,9 @@ int gpg_multi_lkd_batch(gpg_multi* m, int nrows, const double* hp_rows, int row_
  * gpg_predict* keep answering from it until the next gpg_setup_eval / gpg_set_data -- as KernEta_chofac of the
  * reference survives later calc_lkd_all calls. */
 int gpg_setup_eval(gpg_ctx* ctx, const gpg_hp* hp, double beta, double* alpha_out);
+/* The same with a coefficient vector beta [n_beta] (eval_mean_fun_poly, GpMeanFun.py:14-67).  With mean order 1 this is the call
+ * to use: gpg_setup_eval (scalar beta) then returns -1 and says so; with order 0 it reads beta[0]. */
+int gpg_setup_eval_mean(gpg_ctx* ctx, const gpg_hp* hp, const double* beta, double* alpha_out);
 
 /* Replaces GpEvalModel.eval_model(x, calc_grad=False) (GpEvalModel.py:59-198): cross-kernel
  * (GpEvalModel.py:133-139), K^-1 Kyx (GpEvalModel.py:154), mu = beta + Kyx' alpha (:168),
