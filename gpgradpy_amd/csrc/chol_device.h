@@ -7,37 +7,22 @@
 // memory that neither its CU nor its XCD has read before in this launch -- nobody reads a tile before its flag, and
 // tiles / pivot groups do not share cache lines -- so no stale copy can sit in the L1 / L2 it reads through and the
 // agent-scope acquire's `buffer_inv sc1` (invalidate the XCD's whole L2, on every wait of every workgroup) is not
-// needed: ordering against the polling load is enough.  -DGPG_HEAVY_ACQUIRE restores the full fence for A/B runs.
-#ifdef GPG_HEAVY_ACQUIRE
-#define GPG_ACQUIRE() __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent")
-#else
+// needed: ordering against the polling load is enough.
 #define GPG_ACQUIRE() __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup")
-#endif
 
-// Producer side: write the L2's dirty lines back (`buffer_wbl2 sc1`) before the flag goes up; __threadfence() would add
-// the invalidate of an acquire on top.
-#ifdef GPG_HEAVY_RELEASE
-#define GPG_RELEASE() __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent")
-#define GPG_ST(p, v) (*(p) = (v))
-#else
-// Everything another workgroup reads after a flag (factor tiles, reciprocal pivots, solved rows) is stored with
-// GPG_ST: an agent-scope atomic store, i.e. `global_store_dwordx2 ... sc1`, written through the XCD's L2 to memory.
-// The release is then only the wait for those stores (`s_waitcnt vmcnt(0)`) instead of `buffer_wbl2 sc1`, the
-// write-back of every dirty line of the L2.
+// Producer side.  Everything another workgroup reads after a flag (factor tiles, reciprocal pivots, solved rows) is
+// stored with GPG_ST: an agent-scope atomic store, i.e. `global_store_dwordx2 ... sc1`, written through the XCD's L2
+// to memory.  The release is then only the wait for those stores (`s_waitcnt vmcnt(0)`) instead of an agent-scope
+// release fence's `buffer_wbl2 sc1`, the write-back of every dirty line of the L2.
 #define GPG_RELEASE() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
 #define GPG_ST(p, v) gpg_store_through((p), (v))
 __device__ __forceinline__ void gpg_store_through(double* p, double v) {
   __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED,
                      __HIP_MEMORY_SCOPE_AGENT);
 }
-#endif
 // Every thread that wrote part of a tile runs GPG_RELEASE() and the workgroup meets at a barrier before one thread
-// raises the flag, so the flag store itself needs no second write-back.
-#ifdef GPG_HEAVY_RELEASE
-#define GPG_FLAG_UP(p) __hip_atomic_store(p, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT)
-#else
+// raises the flag, so the flag store itself is a relaxed one.
 #define GPG_FLAG_UP(p) __hip_atomic_store(p, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-#endif
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 
@@ -167,14 +152,9 @@ __device__ __forceinline__ int potrf64_wave(const double* src, int sld, double (
 // value is that of wave 0 (other waves return 0).
 // tid_in: index of the calling thread inside its 256-thread team (default: threadIdx.x; the pair kernel runs two teams per workgroup,
 // whose barriers -- __syncthreads, all 512 threads -- coincide because both teams execute the same sequence).
-#ifndef GPG_POTRF_DEFER
-#define GPG_POTRF_DEFER 3        // pivot of the next sub-block at which the previous piece is published (0: right behind its stores, as in rounds 1 / 2)
-#endif
-#if GPG_POTRF_DEFER
-#define GPG_POTRF_BARRIER() GPG_LDS_BARRIER()   // the barriers inside order the LDS image only (src is an LDS tile at every call site); no wait for the stores
-#else
-#define GPG_POTRF_BARRIER() __syncthreads()
-#endif
+// The barriers inside are GPG_LDS_BARRIER: they order the LDS image only (src is an LDS tile at every call site) and do not wait for
+// the stores.
+constexpr int kPotrfDeferPivot = 3;   // pivot of the next sub-block at which the previous piece is published
 __device__ __forceinline__ int potrf64_wg(const double* src, int sld, double (*St)[64], double* __restrict__ blk, int ld,
                                           double* __restrict__ dinv, int* piece_flags = nullptr, int tid_in = -1) {
   const int tid_team = tid_in < 0 ? (int)threadIdx.x : tid_in;
@@ -204,7 +184,7 @@ __device__ __forceinline__ int potrf64_wg(const double* src, int sld, double (*S
 #pragma unroll
         for (int r = 0; r < 4; ++r) St[16 * s + 4 * r + l4][16 * w + l15] = pre[r];
       }
-      GPG_POTRF_BARRIER();                                 // the updated panel is in St[16 s .. 16 s + 15][.]
+      GPG_LDS_BARRIER();                                   // the updated panel is in St[16 s .. 16 s + 15][.]
       if (w == 0) {
 #pragma unroll
         for (int c = 0; c < 16; ++c) a[c] = St[16 * s + c][i];
@@ -215,15 +195,13 @@ __device__ __forceinline__ int potrf64_wg(const double* src, int sld, double (*S
       double ajj = readlane_d(a[0], 16 * s);
 #pragma unroll
       for (int c = 0; c < 16; ++c) {
-#if GPG_POTRF_DEFER
         // the PREVIOUS sub-block's columns went to memory ~1000 cycles ago: their acknowledgements are in (or nearly), the wait costs
         // nothing now -- right behind the stores it cost ~800 cycles of the pivot chain per sub-block (tools/potrf_probe: 28.4 k cycles
         // with the pieces published against 25.1 k without)
-        if (s > 0 && c == GPG_POTRF_DEFER && piece_flags) {
+        if (s > 0 && c == kPotrfDeferPivot && piece_flags) {
           GPG_RELEASE();
           if (i == 0) GPG_FLAG_UP(piece_flags + s - 1);
         }
-#endif
         bad = (bad == 0 && !(ajj > 0.0)) ? 16 * s + c + 1 : bad;
         const double y0 = __builtin_amdgcn_rsq(ajj);
         double g = ajj * y0, h = 0.5 * y0;
@@ -251,7 +229,7 @@ __device__ __forceinline__ int potrf64_wg(const double* src, int sld, double (*S
         if (i >= 16 * s + c) GPG_ST(&blk[i + (size_t)(16 * s + c) * ld], a[c]);
       }
       if (i >= 16 * s && i < 16 * s + 16) GPG_ST(&dinv[i], myinv);
-      if (piece_flags && (!GPG_POTRF_DEFER || s == 3)) {   // pieces 0 .. 2: published from inside the next sub-block's pivot phase
+      if (piece_flags && s == 3) {   // pieces 0 .. 2: published from inside the next sub-block's pivot phase
         GPG_RELEASE();
         if (i == 0) GPG_FLAG_UP(piece_flags + s);
       }
@@ -268,7 +246,7 @@ __device__ __forceinline__ int potrf64_wg(const double* src, int sld, double (*S
       }
     }
     GPG_PS(2 * s + 1)
-    if (s < 3) GPG_POTRF_BARRIER();                        // columns 16 s .. 16 s + 15 of St are final for the next update
+    if (s < 3) GPG_LDS_BARRIER();                          // columns 16 s .. 16 s + 15 of St are final for the next update
   }
   return bad;
 }
@@ -721,12 +699,6 @@ __device__ __forceinline__ int wave_scan_flags(int* const (&rows)[NR], int kdone
   return kend;
 }
 
-// X (128 rows x 128 columns, in place) <- X L^-T against a factorised 128 x 128 diagonal tile, whole workgroup.
-// Each lane quad carries TWO matrix rows (r and r + 64) through the substitution, so the 128 rows cost two
-// substitution sweeps instead of four and half the L-image traffic.  Column block 0 is read from memory
-// straight in the quad layout; block 1 first takes its update X1 L21^T on MFMA (two 64-row passes through
-// the LDS tile).  U: 4 * 16 * 80 doubles, Ls / sdinv: diagonal-block image.  Ends with a workgroup barrier.
-
 // direct_tile_gemm_acc: the MFMA loop of the dataflow kernels, operand fragments straight from global memory:
 // acc (wave tile 64 x 64) += A[64 x 4 nstep] B[64 x 4 nstep]^T, PF k-steps ahead, no LDS; nstep a positive multiple of UN.
 // Lane lane&15 = t owns the two adjacent rows 2t, 2t+1 of each 32-row group of its 64-row slices, so one global_load_dwordx4 feeds two
@@ -740,9 +712,7 @@ __device__ __forceinline__ int wave_scan_flags(int* const (&rows)[NR], int kdone
 //    bytes): global_load ... v_off, s[base] instead of two 64-bit VALU pointer increments per k-step.
 // VALU instructions of one wave take issue slots from the MFMAs of BOTH waves of its SIMD (tools/subst_probe: a wave of fp64 VALU work
 // slows its SIMD partner's MFMA stream from 64 to 96 cycles per instruction).
-#ifndef GPG_KSYNC
-#define GPG_KSYNC 16       // k-steps between two workgroup barriers inside the MFMA loop (0: none; a multiple of PF + 1)
-#endif
+constexpr int GPG_KSYNC = 16;   // k-steps between two workgroup barriers inside the MFMA loop (0: none; a multiple of PF + 1)
 // the barriers of direct_tile_gemm_acc<PF, MI, KS> over nstep k-steps, for a wave that has no MFMA work in this run
 template <int PF, int KS = GPG_KSYNC>
 __device__ __forceinline__ void direct_tile_sync_only(int nstep) {
@@ -760,20 +730,7 @@ __device__ __forceinline__ void direct_tile_negate(d4 (&acc)[4][4]) {
 }
 // MI = 4: all 64 rows of the wave tile; MI = 2: only its first 32-row group (acc[.][0], acc[.][1]) -- the right-hand-side tile row of
 // the factorisation carries two real rows.
-#ifndef GPG_UNROLL_KSTEPS
-#define GPG_UNROLL_KSTEPS 32
-#endif
-typedef double gpg_d2v __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ double2 gpg_dx_nt(const char* p) {
-  const gpg_d2v v = __builtin_nontemporal_load(reinterpret_cast<const gpg_d2v*>(p));
-  double2 r; r.x = v.x; r.y = v.y; return r;
-}
-__device__ __forceinline__ double2 gpg_dx_x2(const char* p, unsigned l0, unsigned l8) {   // two 8-byte loads (l8 = l0 + 8, opaque to the compiler)
-  double2 r;
-  r.x = *reinterpret_cast<const double*>(p + (size_t)l0);
-  r.y = *reinterpret_cast<const double*>(p + (size_t)l8);
-  return r;
-}
+constexpr int GPG_UNROLL_KSTEPS = 32;   // k-steps of straight-line code per trip of the MFMA loop
 template <int PF, int MI = 4, int KS = GPG_KSYNC, int UN = GPG_UNROLL_KSTEPS>
 __device__ __forceinline__ void direct_tile_gemm_acc(d4 (&acc)[4][4], const double* ua_d, unsigned la, int lda, const double* ub_d,
                                                      unsigned lb, int ldb, int nstep) {
@@ -781,17 +738,7 @@ __device__ __forceinline__ void direct_tile_gemm_acc(d4 (&acc)[4][4], const doub
   const char* ua = reinterpret_cast<const char*>(ua_d);
   const char* ub = reinterpret_cast<const char*>(ub_d);
   double2 fa0[PF + 1], fa1[PF + 1], fb0[PF + 1], fb1[PF + 1];
-#if defined(GPG_DX_X2)
-  unsigned la8 = la + 8u, lb8 = lb + 8u;
-  asm volatile("" : "+v"(la8), "+v"(lb8));
-#endif
-#if defined(GPG_DX_NT)        // diagnostic builds of tools/subst_probe.hip only: other flavours of the operand loads
-#define GPG_DX_LD(u, l, x) gpg_dx_nt((u) + (size_t)(l) + (x))
-#elif defined(GPG_DX_X2)
-#define GPG_DX_LD(u, l, x) gpg_dx_x2((u) + (x), (l), (l##8))
-#else
 #define GPG_DX_LD(u, l, x) (reinterpret_cast<const double2*>((u) + (size_t)(l))[(x) / 16])
-#endif
 #define GPG_DX_LOAD(set)                                                              \
   {                                                                                   \
     fa0[set] = GPG_DX_LD(ua, la, 0);                                                  \

@@ -245,7 +245,6 @@ gemm_dma_kernel(double* __restrict__ C, int ldc, const double* __restrict__ A, i
 #endif
   d4 acc[4][4] = {};
   double* Cw = C + (size_t)(m0 + wm * 64 + l15) + (size_t)(n0 + wn * 64 + l4) * ldc;
-#ifndef GPG_ABLATE_CLOAD
   if (wave_active) {
 #pragma unroll
     for (int ni = 0; ni < 4; ++ni)
@@ -254,7 +253,6 @@ gemm_dma_kernel(double* __restrict__ C, int ldc, const double* __restrict__ A, i
 #pragma unroll
         for (int r = 0; r < 4; ++r) acc[ni][mi][r] = Cw[mi * 16 + (size_t)(ni * 16 + 4 * r) * ldc];
   }
-#endif
 
   // per-lane DMA sources: this wave moves k-rows w and w + 4 of every chunk, for A and for B
   int rowa = m0 + 2 * lane;
@@ -264,9 +262,6 @@ gemm_dma_kernel(double* __restrict__ C, int ldc, const double* __restrict__ A, i
   const size_t a4 = (size_t)4 * lda, b4 = (size_t)4 * ldb, aK = (size_t)KB * lda, bK = (size_t)KB * ldb;
   double* const sbase = smem;
 
-#ifdef GPG_ABLATE_DMA
-#define GPG_DMA_ISSUE(stage) {}
-#else
 #define GPG_DMA_ISSUE(stage)                                                                              \
   {                                                                                                       \
     double* sa = sbase + (stage) * STAGE + w * ROW;                                                        \
@@ -277,7 +272,6 @@ gemm_dma_kernel(double* __restrict__ C, int ldc, const double* __restrict__ A, i
     ga += aK;                                                                                             \
     gb += bK;                                                                                             \
   }
-#endif
 #define GPG_DMA_COMPUTE(stage)                                                                            \
   {                                                                                                       \
     const double* pa = sbase + (stage) * STAGE + l4 * ROW + wm * 64 + l15;                                 \
@@ -476,7 +470,7 @@ void launch_gemm(gpg_ctx* c, double* C, int ldc, const double* A, int lda, const
 // skipT x skipT leading block dropped), ordered by 4 x 4 super-tiles.  Built once per shape and kept on
 // the device for the lifetime of the context.
 const TileMap& get_tilemap(gpg_ctx* c, int Mt, int Nt, int skipT) {
-  const unsigned long long key = ((unsigned long long)Mt << 40) | ((unsigned long long)Nt << 16) | (unsigned)skipT;
+  const TaskListKey key{GPG_LIST_TRAILING, 0, skipT, 0, Mt, Nt};
   auto it = c->tilemaps.find(key);
   if (it != c->tilemaps.end()) return it->second;
   constexpr int S = 4;

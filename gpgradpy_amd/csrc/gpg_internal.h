@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <map>
 #include <string>
+#include <tuple>
 #include <vector>
 #include "../../include/gpgrad.h"
 
@@ -33,6 +34,16 @@ struct gpg_batch_item { AsmParams p; double var_fval, var_fgrad; };
 
 struct TileMap { int* dev; int n; };
 
+// What a cached device list (gpg_ctx::tilemaps) was built for.  variant: fused sub-diagonal tiles (64-tile factorisation), tile pairs
+// (128-tile factorisation), W on 64 x 64 tiles (inverse), leading tiles skipped (trailing update); fields a list does not depend on are 0.
+enum { GPG_LIST_TRAILING, GPG_LIST_CHOL, GPG_LIST_CHOL_BATCH64, GPG_LIST_CHOL_BATCH128, GPG_LIST_INVERSE, GPG_LIST_LOWER_TRI };
+struct TaskListKey {
+  int kind, order, variant, B, Mt, Rt;
+  bool operator<(const TaskListKey& o) const {
+    return std::tie(kind, order, variant, B, Mt, Rt) < std::tie(o.kind, o.order, o.variant, o.B, o.Mt, o.Rt);
+  }
+};
+
 struct ProfEvent { hipEvent_t e0, e1; int cat; };
 
 // One factorisation workspace with the vectors that belong to the matrix in it.  The context keeps two: set 0 serves the
@@ -54,7 +65,7 @@ struct gpg_ctx {
   int lookahead = 1;
   int gemm_impl = 1;                 // 1: LDS-DMA ring kernel for the 128x128 updates, 0: register-staged kernel (A/B runs)
   std::vector<hipEvent_t> ev_panel, ev_upd;
-  std::map<unsigned long long, TileMap> tilemaps;   // live-tile lists of the trailing updates, per shape
+  std::map<TaskListKey, TileMap> tilemaps;   // task / live-tile lists on the device, per shape (kept for the context's lifetime)
   int n = 0, d = 0, use_grad = 0, kernel = 0;
   int N = 0, Npad = 0, R = GPG_RHS_ROWS, ld = 0;
   int ng = 0;                // gradient points in use (KernelSqExp.py:349-377: bvec_use_grad)

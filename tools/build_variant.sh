@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B builds of the library with extra -D switches, next to the product build (never loaded unless GPG_LIB names it):
-#   tools/build_variant.sh nopersist -DGPG_NO_PERSIST      ->  gpgradpy_amd/libgpgrad_hip_nopersist.so
+#   tools/build_variant.sh stamp -DGPG_STAMP      ->  gpgradpy_amd/libgpgrad_hip_stamp.so
 # Built in a scratch copy of csrc/ so that the product's objects are untouched.
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)

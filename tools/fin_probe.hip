@@ -1,7 +1,7 @@
 // Diagnostic (not product code): the off-diagonal finalisation X <- X L^-T of one 128 x 128 tile against a finished 128 x 128
 // diagonal tile, timed inside a workload that looks like the factorisation (every workgroup alternates a burst of the
 // direct-fragment MFMA loop with one finalisation; two workgroups per CU, out of phase), in two versions:
-//   mode 0  the product's: accumulators -> memory -> quad-row VALU substitution (tile_solve_rows128)
+//   mode 0  the product's of rounds 1 / 2: accumulators -> memory -> quad-row VALU substitution (tile_solve_rows128, below)
 //   mode 1  MFMA-blocked, on the accumulators as the MFMA loop leaves them: rank-8 steps -- the 8 x 8 diagonal blocks by exact VALU
 //           substitution across the four lane groups, everything below them by v_mfma_f64_16x16x4 with the finished accumulator
 //           registers as B operands (register r of a 16 x 16 D tile holds rows 4r..4r+3 in the B-operand layout) and -L from an LDS
@@ -19,6 +19,103 @@ void gpg_prof_end(gpg_ctx*) {}
 void gpg_launch_identity(gpg_ctx*, double*, int) {}
 
 namespace {
+// X (128 rows x 128 columns, in place) <- X L^-T against a factorised 128 x 128 diagonal tile, whole workgroup.
+// Each lane quad carries TWO matrix rows (r and r + 64) through the substitution, so the 128 rows cost two
+// substitution sweeps instead of four and half the L-image traffic.  Column block 0 is read from memory
+// straight in the quad layout; block 1 first takes its update X1 L21^T on MFMA (two 64-row passes through
+// the LDS tile).  U: 4 * 16 * 80 doubles, Ls / sdinv: diagonal-block image.  Ends with a workgroup barrier.
+// (Until round 3 the finalisation of tile128_trinv_kernel, with a constant array of ones as the piece flags pa / flag_c / pb.)
+__device__ __forceinline__ int tile_solve_rows128(const double* L, int ldl, const double* dinv, double* X, int ldx, double* U,
+                                                  double (*Ls)[4][18], double* sdinv, int* pa, int* flag_c, int* pb,
+                                                  int* abort_word, int* info, int* sh) {
+  constexpr int SA = 80, BUF = 16 * SA;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int l15 = lane & 15, l4 = lane >> 4;
+  const int q = tid & 3, rr = tid >> 2;
+  const int sp = tid & 31, sk = tid >> 5;
+  double x0[16], x1[16];
+  // ---- column block 0 ----------------------------------------------------------------------------------------
+  {
+    const double* Xr = X + rr + (size_t)q * ldx;     // own rows: in flight while the flag is polled
+#pragma unroll
+    for (int m = 0; m < 16; ++m) {
+      x0[m] = Xr[(size_t)(4 * m) * ldx];
+      x1[m] = Xr[64 + (size_t)(4 * m) * ldx];
+    }
+  }
+  // L11 arrives in four 16-column pieces (pa[0..3]) while the diagonal tile is still in its first potrf64
+#define GPG_T128_PIECE(FL, LP, DOFF, S)                                                      \
+  {                                                                                         \
+    if (!wg_wait_flag((FL) + (S), abort_word, info, sh)) return 0;                           \
+    _Pragma("unroll") for (int u = 0; u < 4; ++u) {                                          \
+      const int t = tid + 256 * u, jj = 16 * (S) + (t >> 6), k = t & 63;                     \
+      Ls[jj][k & 3][k >> 2] = (LP)[k + (size_t)jj * ldl];                                    \
+    }                                                                                       \
+    if (tid < 16) sdinv[16 * (S) + tid] = dinv[(DOFF) + 16 * (S) + tid];                     \
+    __syncthreads();                                                                        \
+    GPG_QUAD_SUBST2_PIECE(x0, x1, Ls, sdinv, q, S)                                           \
+    _Pragma("unroll") for (int m = 0; m < 16; ++m) { asm volatile("" : "+v"(x0[m])); asm volatile("" : "+v"(x1[m])); } \
+  }
+  GPG_T128_PIECE(pa, L, 0, 0)
+  GPG_T128_PIECE(pa, L, 0, 1)
+  GPG_T128_PIECE(pa, L, 0, 2)
+  GPG_T128_PIECE(pa, L, 0, 3)
+  {
+    double* Xr = X + rr + (size_t)q * ldx;
+#pragma unroll
+    for (int m = 0; m < 16; ++m) {
+      GPG_ST(&Xr[(size_t)(4 * m) * ldx], x0[m]);
+      GPG_ST(&Xr[64 + (size_t)(4 * m) * ldx], x1[m]);
+    }
+  }
+  if (!wg_wait_flag(flag_c, abort_word, info, sh)) return 0;   // barrier inside: X1 visible to the workgroup, Ls free
+  // ---- column block 1: T2 -= X1 L21^T for the two row halves, each transposed through the LDS tile ---------------
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    d4 acc[4];
+    const double* Cw = X + 64 * h + 16 * w + l15 + (size_t)(64 + l4) * ldx;
+#pragma unroll
+    for (int ni = 0; ni < 4; ++ni)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc[ni][r] = Cw[(size_t)(ni * 16 + 4 * r) * ldx];
+    wave_tile_gemm(acc, X + 64 * h + 2 * sp + (size_t)sk * ldx, ldx, L + 64 + 2 * sp + (size_t)sk * ldl, ldl, 4, U, U + 2 * BUF,
+                   w, l15, l4, sp, sk);
+    __syncthreads();
+#pragma unroll
+    for (int ni = 0; ni < 4; ++ni)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) U[(ni * 16 + 4 * r + l4) * SA + 16 * w + l15] = acc[ni][r];
+    __syncthreads();
+    const double* Tr = U + q * SA + rr;
+    if (h == 0) {
+#pragma unroll
+      for (int m = 0; m < 16; ++m) x0[m] = Tr[(4 * m) * SA];
+    } else {
+#pragma unroll
+      for (int m = 0; m < 16; ++m) x1[m] = Tr[(4 * m) * SA];
+    }
+    __syncthreads();   // tile consumed before the next pass stages into U again
+  }
+  {   // L22 in four pieces (pb[0..3]) while the diagonal tile is in its second potrf64
+    const double* L22 = L + 64 + (size_t)64 * ldl;
+    GPG_T128_PIECE(pb, L22, 64, 0)
+    GPG_T128_PIECE(pb, L22, 64, 1)
+    GPG_T128_PIECE(pb, L22, 64, 2)
+    GPG_T128_PIECE(pb, L22, 64, 3)
+  }
+#undef GPG_T128_PIECE
+  {
+    double* Xr = X + rr + (size_t)(64 + q) * ldx;
+#pragma unroll
+    for (int m = 0; m < 16; ++m) {
+      GPG_ST(&Xr[(size_t)(4 * m) * ldx], x0[m]);
+      GPG_ST(&Xr[64 + (size_t)(4 * m) * ldx], x1[m]);
+    }
+  }
+  __syncthreads();
+  return 1;
+}
+
 constexpr int FLD = 66;                                   // leading dimension of the LDS image of a 64 x 64 diagonal block
 __shared__ __attribute__((aligned(16))) double fin_Lc[64 * FLD];   // Lc[c * FLD + r] = L[r][c] (r >= c), 0 above the diagonal
 __shared__ double fin_dinv[64];
