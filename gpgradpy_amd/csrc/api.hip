@@ -176,6 +176,22 @@ static void finish_lkd(const gpg_ctx* c, const gpg_hp* hp, const double* s, int 
   }
 }
 
+// Buffers of the posterior at nxp (a multiple of 64) query rows; grown, never shrunk.
+int gpg_predict_bufs(gpg_ctx* c, int nxp) {
+  if (nxp <= c->xq_cap) return 0;
+  if (c->Wt) (void)hipFree(c->Wt);
+  if (c->xq_dev) (void)hipFree(c->xq_dev);
+  if (c->musig) (void)hipFree(c->musig);
+  if (c->gradbuf) (void)hipFree(c->gradbuf);
+  c->Wt = c->xq_dev = c->musig = c->gradbuf = nullptr; c->xq_cap = 0;
+  GPG_HIP_OK(c, hipMalloc(&c->Wt, sizeof(double) * (size_t)nxp * c->Npad));
+  GPG_HIP_OK(c, hipMalloc(&c->xq_dev, sizeof(double) * (size_t)nxp * c->d));
+  GPG_HIP_OK(c, hipMalloc(&c->musig, sizeof(double) * 2 * nxp));
+  GPG_HIP_OK(c, hipMalloc(&c->gradbuf, sizeof(double) * ((size_t)2 * nxp * GPG_MAX_DIM + (size_t)nxp * 64)));
+  c->xq_cap = nxp;
+  return 0;
+}
+
 extern "C" {
 
 int gpg_create(gpg_ctx** out, int device, int n_eval, int dim, int use_grad, int kernel) {
@@ -270,7 +286,7 @@ void gpg_destroy(gpg_ctx* c) {
                     c->ws[1].A, c->ws[1].dvec, c->ws[1].invp, c->ws[1].zvec, c->ws[1].tmpv, c->ws[1].dinv,
                     c->Xt, c->y, c->noise, c->scal, c->eval_beta_dev, c->Wt, c->xq_dev,
                     c->musig, c->gradbuf, c->dense_tmp, c->Wfull, c->Minv, c->gpartial, c->batchA, c->batchV, c->vec_rows, c->vec_x, c->apply_buf,
-                    c->batchW, c->batchM, c->batchZ, c->gres, c->Kbuf, c->Tbuf};
+                    c->batchW, c->batchM, c->batchZ, c->gres, c->Kbuf, c->Tbuf, c->jbuf};
   for (double* b : bufs) if (b) (void)hipFree(b);
   if (c->info) (void)hipFree(c->info);
   if (c->gpos) (void)hipFree(c->gpos);
@@ -987,18 +1003,7 @@ static int predict_impl(gpg_ctx* c, int nx, const double* xq, double varK, doubl
   GPG_HIP_OK(c, hipSetDevice(c->device));
   GPG_WS(c, 1);
   const int nxp = ((nx + 63) / 64) * 64;
-  if (nxp > c->xq_cap) {
-    if (c->Wt) (void)hipFree(c->Wt);
-    if (c->xq_dev) (void)hipFree(c->xq_dev);
-    if (c->musig) (void)hipFree(c->musig);
-    if (c->gradbuf) (void)hipFree(c->gradbuf);
-    c->Wt = c->xq_dev = c->musig = c->gradbuf = nullptr; c->xq_cap = 0;
-    GPG_HIP_OK(c, hipMalloc(&c->Wt, sizeof(double) * (size_t)nxp * c->Npad));
-    GPG_HIP_OK(c, hipMalloc(&c->xq_dev, sizeof(double) * (size_t)nxp * c->d));
-    GPG_HIP_OK(c, hipMalloc(&c->musig, sizeof(double) * 2 * nxp));
-    GPG_HIP_OK(c, hipMalloc(&c->gradbuf, sizeof(double) * ((size_t)2 * nxp * GPG_MAX_DIM + (size_t)nxp * 64)));
-    c->xq_cap = nxp;
-  }
+  if (int rc = gpg_predict_bufs(c, nxp)) return rc;
   // the allocation may be larger than this call's nxp: kernels index with this call's nxp
   std::vector<double> xt((size_t)nxp * c->d, 0.0);
   for (int j = 0; j < nx; ++j)
@@ -1512,3 +1517,7 @@ int gpg_device_info(int device, char* buf, int buflen) {
 }
 
 }  // extern "C"
+
+// for the API calls that live in other translation units (joint.hip)
+int gpg_with_fallback(gpg_ctx* c, const std::function<int()>& f) { return with_fallback(c, f); }
+int gpg_solve_failure(gpg_ctx* c) { return solve_failure(c); }

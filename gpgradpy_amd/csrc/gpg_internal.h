@@ -1,6 +1,7 @@
 // Internal declarations shared by the HIP translation units of libgpgrad_hip.so (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <functional>
 #include <map>
 #include <string>
 #include <tuple>
@@ -140,6 +141,9 @@ struct gpg_ctx {
   double* musig = nullptr;   // [2 x nxp]
   double* gradbuf = nullptr; // [2 x nxp x d] posterior-gradient reductions + [nxp x 64] backward-solve scratch
   int xq_cap = 0;
+  double* jbuf = nullptr;    // scratch of gpg_predict_joint: Gram partials | Kqq | difference tensor | cov | mean partials (on first use)
+  size_t jbuf_bytes = 0;
+  int gram_splits = 0;       // K-chunks of rows_gram_splitk_kernel (gpg_set_gram_splits; 0 = from the shape)
   double* batchA = nullptr;     // [batch_cap x A_elems] workspaces of the batched small-matrix factorisation (on first use)
   double* batchV = nullptr;     // [batch_cap x 3 x Npad] dvec / invp / dinv of each batched matrix
   int batch_cap = 0;
@@ -246,6 +250,9 @@ int gpg_kern_rtensor_dhp_run(int kernel, int d, int n, int use_grad, const doubl
                              double* out_th_dev, double* out_al_dev, hipStream_t stream);
 int gpg_kern_rtensor_hess_x_run(int kernel, int d, int n1, int n2, int n2g, int use_grad, const double* theta, double hp_kernel,
                                 const double* rt_dev, const int* gpos2_dev, double* out_dev, hipStream_t stream);
+int gpg_with_fallback(gpg_ctx* c, const std::function<int()>& f);       // api.hip: repeat a call whose dataflow launch timed out (-4)
+int gpg_solve_failure(gpg_ctx* c);                                        // api.hip: -4 when *h_info reports a timed-out dataflow solve
+int gpg_predict_bufs(gpg_ctx* c, int nxp);                                // api.hip: Wt / xq_dev / musig / gradbuf for nxp query rows
 int gpg_ws_activate(gpg_ctx* c, int which);                              // make workspace set `which` the active one (allocates set 1 on first use)
 
 // Device allocation inside a launch helper (task lists, flags, carrier tiles): on failure the pointer stays null, the

@@ -17,6 +17,7 @@ from . import _lib
 from .hpara import HparaOptzInfo, HparaOptzVal, LkdInfo
 from .rescaling import Rescaling, calc_dist_min, calc_dist_max
 from .hpara_optz import HparaOptz
+from .joint import draw_from_joint
 
 
 class DeviceChoFactor:
@@ -1313,6 +1314,61 @@ class GaussianProcess(HparaOptz):
         if squeeze_nx:
             return sig2[0], (dsig2dx[0, :] if calc_grad else None), None
         return sig2, dsig2dx, None
+
+    def eval_model_joint(self, x2model_in, calc_grad=False):
+        """Joint posterior of the latent function at the nx query points (include/gpgrad.h: gpg_predict_joint): returns
+        (mean [m], cov [m, m]) with m = nx, or m = nx (dim + 1) with calc_grad: rows derivative-major like the training data,
+        row blk * nx + j = f(x_j) for blk = 0 and d f / d x_(blk-1) at x_j otherwise.  cov = varK (Kqq - Kqy Kcov^-1 Kyq) is
+        exactly symmetric and not clipped; the uncertainty of the mean coefficients is not part of it (as in eval_model)."""
+        assert self.KernEta_chofac is not None, 'To evaluate the surr the Cholesky decomposition is required'
+        if x2model_in.ndim == 1:
+            x2model = x2model_in[None, :]
+        elif x2model_in.ndim == 2:
+            x2model = x2model_in
+        else:
+            raise Exception(f'x2model_in should be a 2d array but it has shape {x2model_in.shape}')
+        if (self.hp_vals == self._hp_vals_model_setup) is False:
+            raise Exception('Cannot change hp_vals between calling setup_eval_model() and eval_model()')
+        if self.b_use_data_scl:
+            raise Exception('The method eval_model_joint() is not setup for cases where data must be rescaled')
+        if not self._eval_ready:
+            raise Exception('setup_eval_model() must be called (again): set_data() replaced the data of the device model')
+        nx = x2model.shape[0]
+        m = nx * (self.dim + 1) if calc_grad else nx
+        if m > 4096:                                          # before the [m, m] host array is made
+            raise _lib.GpgError(f'eval_model_joint: {m} joint rows, at most 4096 are supported')
+        xq = np.ascontiguousarray(x2model, dtype=np.float64)
+        mean, cov = np.empty(m), np.empty((m, m))
+        rc = self._lib.gpg_predict_joint(self._ctx, nx, _lib.as_dp(xq), float(self.hp_vals.varK), int(bool(calc_grad)),
+                                         _lib.as_dp(mean), _lib.as_dp(cov))
+        if rc != 0:
+            raise _lib.GpgError(f'gpg_predict_joint failed ({rc}): {self._err()}')
+        return mean, cov
+
+    def sample_posterior(self, x2model_in, n_samples, calc_grad=False, seed=None, z=None):
+        """Draws from the joint posterior at the query points: (f_samples [n_samples, nx], g_samples [n_samples, nx, dim] or
+        None without calc_grad).  z: optional [n_samples, m] standard normals in the row order of eval_model_joint;
+        otherwise np.random.default_rng(seed).standard_normal.  The covariance comes from the device, the draw itself is
+        host arithmetic (gpgradpy_amd/joint.py)."""
+        mean, cov = self.eval_model_joint(x2model_in, calc_grad=calc_grad)
+        m = mean.size
+        nx = m // (self.dim + 1) if calc_grad else m
+        if z is None:
+            z = np.random.default_rng(seed).standard_normal((int(n_samples), m))
+        else:
+            z = np.asarray(z, dtype=np.float64)
+            if z.shape != (int(n_samples), m):
+                raise ValueError(f'z must have shape ({int(n_samples)}, {m}), got {z.shape}')
+        s = draw_from_joint(mean, cov, z)
+        if not calc_grad:
+            return s, None
+        return s[:, :nx], np.transpose(s[:, nx:].reshape(-1, self.dim, nx), (0, 2, 1))
+
+    def set_gram_splits(self, n):
+        """K-chunks of the Gram kernel behind eval_model_joint (include/gpgrad.h: gpg_set_gram_splits; 0 = from the shape)."""
+        rc = self._lib.gpg_set_gram_splits(self._ctx, int(n))
+        if rc != 0:
+            raise _lib.GpgError(f'gpg_set_gram_splits failed ({rc}): {self._err()}')
 
     def shard_restarts(self, group):
         """Opt in to sharding the restart rows of `set_hpara('optz')` (the hp_best pre-selection and the SLSQP

@@ -207,6 +207,31 @@ int gpg_predict_var(gpg_ctx* ctx, int nx, const double* xq, double varK, double*
 int gpg_predict_hess(gpg_ctx* ctx, const double* xq, double varK, double* mu, double* sig, double* dmudx,
                      double* dsigdx, double* d2mudx2, double* d2sigdx2);
 
+/* Joint posterior at nx query points, from the factor kept by gpg_setup_eval.
+ * with_grad = 0: m = nx rows (function values).
+ * with_grad = 1: m = nx (dim + 1) rows, derivative-major like the training data:
+ *   row r = blk * nx + j, blk 0 = f(x_j), blk k+1 = d f / d x_k at x_j.
+ * mean [m]; cov [m, m] row-major, exactly symmetric:
+ *   cov = varK (Kqq - Kqy Kcov^-1 Kyq)
+ * Kqq: the kernel matrix of the query points with themselves (no nugget, no noise: the latent function).
+ * Kqy: the cross-covariance that gpg_predict_grad already uses (training-side gradient mask honoured); it also works for a
+ *   model built without training gradients (use_grad = 0) and with_grad = 1.
+ * Kcov: the matrix gpg_setup_eval factorised.
+ * mean includes the mean function: beta_0 (+ xq . beta_1..d, and beta_k on the gradient rows, with mean order 1).
+ * As in the reference, the uncertainty of the mean coefficients is NOT included.
+ * Not clipped: tiny negative diagonal entries are returned as computed.
+ * mean or cov may be NULL.  m padded to a multiple of 64 must be <= 4096 (-1 beyond), and gpg_setup_eval must have succeeded (-1).
+ * On the device: the cross-covariance rows of all points and blocks, one multi-row forward sweep Z = Kqy P^-1 L^-T, then
+ * G = Z Z^T by a split-K fp64 MFMA kernel on the lower 64 x 64 tiles (partials added in fixed chunk order by a second launch,
+ * which also subtracts from Kqq and mirrors the tile): ordinary grids, no atomics, so the result is the same bits from run to
+ * run and under any gpg_set_max_workgroups. */
+int gpg_predict_joint(gpg_ctx* ctx, int nx, const double* xq, double varK, int with_grad, double* mean, double* cov);
+
+/* Number of K-chunks of the Gram kernel of gpg_predict_joint: 0 = automatic, a function of (m, N_pad) only -- never of the
+ * device, the grid or gpg_set_max_workgroups; n >= 1: that many, capped at N_pad / 64.  Different chunk counts add the same
+ * products in a different order: results agree to rounding, not bitwise. */
+int gpg_set_gram_splits(gpg_ctx* ctx, int n);
+
 /* Materialisation on request (the 7-tuple of Kernel.py:307 carries N x N arrays; the fast path never
  * copies them).  out is [N, N] column-major == row-major (symmetric) for which = 0..2:
  *   0 Kern (Kernel.py:213-216), 1 Kcov (Kernel.py:237 / 277), 2 the matrix that is factorised
