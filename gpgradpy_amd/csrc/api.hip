@@ -288,6 +288,7 @@ void gpg_destroy(gpg_ctx* c) {
                     c->musig, c->gradbuf, c->dense_tmp, c->Wfull, c->Minv, c->gpartial, c->batchA, c->batchV, c->vec_rows, c->vec_x, c->apply_buf,
                     c->batchW, c->batchM, c->batchZ, c->gres, c->Kbuf, c->Tbuf, c->jbuf};
   for (double* b : bufs) if (b) (void)hipFree(b);
+  gpg_meanunc_free(c);
   if (c->info) (void)hipFree(c->info);
   if (c->gpos) (void)hipFree(c->gpos);
   bool parked = false;
@@ -928,11 +929,13 @@ int gpg_lkd_grad_batch(gpg_ctx* c, int m, const double* hp_rows, int row_len, do
 }
 int gpg_setup_eval(gpg_ctx* c, const gpg_hp* hp, double beta, double* alpha_out) {
   if (c && c->mean_order != 0) { c->err = "gpg_setup_eval takes a scalar beta: with mean order 1 call gpg_setup_eval_mean (beta [dim + 1])"; return -1; }
+  if (c) c->mu_ready = false;   // the mean-uncertainty state belongs to the factor that is replaced now
   return with_fallback(c, [&] { return gpg_setup_eval_once(c, hp, beta, nullptr, alpha_out); });
 }
 int gpg_setup_eval_mean(gpg_ctx* c, const gpg_hp* hp, const double* beta, double* alpha_out) {
   if (!c) return -1;
   if (!beta) { c->err = "beta is NULL"; return -1; }
+  c->mu_ready = false;
   if (c->mean_order == 0) return with_fallback(c, [&] { return gpg_setup_eval_once(c, hp, beta[0], nullptr, alpha_out); });
   return with_fallback(c, [&] { return gpg_setup_eval_once(c, hp, 0.0, beta, alpha_out); });
 }
@@ -1004,6 +1007,11 @@ static int predict_impl(gpg_ctx* c, int nx, const double* xq, double varK, doubl
   GPG_WS(c, 1);
   const int nxp = ((nx + 63) / 64) * 64;
   if (int rc = gpg_predict_bufs(c, nxp)) return rc;
+  const bool munc = c->mean_unc != 0;
+  const int nb = c->n_beta;
+  if (munc) {   // W_V, K^-1 V, H of this posterior (built by the first call after gpg_setup_eval; uses and clears Wt)
+    if (int rc = gpg_meanunc_ensure(c)) return rc;
+  }
   // the allocation may be larger than this call's nxp: kernels index with this call's nxp
   std::vector<double> xt((size_t)nxp * c->d, 0.0);
   for (int j = 0; j < nx; ++j)
@@ -1016,16 +1024,21 @@ static int predict_impl(gpg_ctx* c, int nx, const double* xq, double varK, doubl
   gpg_launch_predict_reduce(c, nx, nxp, c->eval_beta, varK, 0);
   gpg_forward_rows(c, c->Wt, nxp, nxp, nx);
   gpg_launch_predict_reduce(c, nx, nxp, c->eval_beta, varK, 1);
+  if (munc) {   // u = v - W_V' z per row, c = H^-1 u, q = u' H^-1 u
+    if (int rc = gpg_meanunc_rows(c, c->Wt, nxp, nx, nx)) return rc;
+  }
   std::vector<double> hgrad_vec;
   double* hgrad = nullptr;
   size_t n_hgrad = 0;
-  double* pin = pinned_scratch(c, 2 * (size_t)nxp * (1 + GPG_MAX_DIM));   // mu | sig2 | the two gradient blocks
+  const size_t n_pin = 2 * (size_t)nxp * (1 + GPG_MAX_DIM), n_hmu = munc ? (size_t)(nb + 1) * nxp : 0;
+  double* pin = pinned_scratch(c, n_pin + n_hmu);   // mu | sig2 | the two gradient blocks | mean uncertainty: c [nb x nxp] | q [nxp]
   if (dmudx) {
     // K^-1 Kyx needs the second triangular sweep too (GpEvalModel.py:154), then the fused gradient reductions
     double* g1 = c->gradbuf;
     double* g2 = c->gradbuf + (size_t)nxp * GPG_MAX_DIM;
     double* tbuf = c->gradbuf + (size_t)2 * nxp * GPG_MAX_DIM;
     gpg_backward_rows(c, c->Wt, nxp, nx, tbuf);
+    if (munc) gpg_meanunc_update_rows(c, c->Wt, nxp, nx);   // K^-1 k + K^-1 V H^-1 u
     gpg_launch_cross_grad(c, p, nx, nxp, g1, g2);
     n_hgrad = (size_t)2 * nxp * GPG_MAX_DIM;
     hgrad = pin ? pin + 2 * (size_t)nxp : nullptr;
@@ -1036,12 +1049,25 @@ static int predict_impl(gpg_ctx* c, int nx, const double* xq, double varK, doubl
   double* host = pin;
   if (!host) { host_vec.resize(2 * (size_t)nxp); host = host_vec.data(); }
   GPG_HIP_OK(c, hipMemcpyAsync(host, c->musig, sizeof(double) * 2 * nxp, hipMemcpyDeviceToHost, c->stream));
+  std::vector<double> hmu_vec;
+  double* hmu = pin ? pin + n_pin : nullptr;
+  if (munc) {
+    if (!hmu) { hmu_vec.resize(n_hmu); hmu = hmu_vec.data(); }
+    GPG_HIP_OK(c, hipMemcpyAsync(hmu, c->mu_cb, sizeof(double) * n_hmu, hipMemcpyDeviceToHost, c->stream));
+  }
   GPG_HIP_OK(c, hipMemcpyAsync(c->h_info, c->info, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   GPG_HIP_OK(c, hipStreamSynchronize(c->stream));
   GPG_HIP_OK(c, hipGetLastError());
   GPG_LAUNCH_OK(c);
   if (solve_failure(c)) return -4;
   const double sigK = sqrt(varK);
+  if (munc) {   // sig2 / varK += u' H^-1 u; the gradient sum loses (H^-1 u)_(k+1), the derivative of the basis [1, x] (order 1 only)
+    for (int j = 0; j < nx; ++j) {
+      host[nxp + j] += hmu[(size_t)nb * nxp + j];
+      if (dmudx && nb > 1)
+        for (int k = 0; k < c->d; ++k) hgrad[(size_t)nxp * GPG_MAX_DIM + (size_t)j * c->d + k] -= hmu[(size_t)(k + 1) * nxp + j];
+    }
+  }
   for (int j = 0; j < nx; ++j) {
     mu[j] = host[j];
     double s2 = host[nxp + j];
@@ -1084,6 +1110,16 @@ static int predict_hess_once(gpg_ctx* c, const double* xq, double varK, double* 
   gpg_launch_hess_stage(c, p, nxp, h1, h2, T, 1);
   gpg_forward_rows(c, c->Wt, nxp, nxp, d + 1);
   gpg_launch_hess_stage(c, p, nxp, h1, h2, T, 2);
+  // mean uncertainty: row 0 of Wt was t = K^-1 k + K^-1 V H^-1 u already (stage 0); the rows d_i u = e_(i+1) - W_V' z_i of the
+  // swept derivative rows 1 .. d give the last term, 2 d_i u' H^-1 d_k u = 2 c'_i . c'_k
+  const bool munc = c->mean_unc != 0;
+  const int nb = c->n_beta;
+  std::vector<double> hcf;
+  if (munc) {
+    if (int rc2 = gpg_meanunc_rows(c, c->Wt, nxp, d + 1, 1)) return rc2;
+    hcf.resize((size_t)nb * nxp);
+    GPG_HIP_OK(c, hipMemcpyAsync(hcf.data(), c->mu_cf, sizeof(double) * hcf.size(), hipMemcpyDeviceToHost, c->stream));
+  }
   std::vector<double> h(3 * GPG_MAX_DIM * GPG_MAX_DIM);
   GPG_HIP_OK(c, hipMemcpyAsync(h.data(), h1, sizeof(double) * h.size(), hipMemcpyDeviceToHost, c->stream));
   GPG_HIP_OK(c, hipMemcpyAsync(c->h_info, c->info, sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -1098,7 +1134,12 @@ static int predict_hess_once(gpg_ctx* c, const double* xq, double varK, double* 
   for (int k = 0; k < d; ++k)
     for (int i = 0; i < d; ++i) {
       d2mudx2[k * d + i] = H1[k * d + i];                                               // GpEvalModel.py:355-363
-      const double d2s2 = -2.0 * varK * (H2[k * d + i] + TT[k * d + i]);                // :370-372
+      double d2s2 = -2.0 * varK * (H2[k * d + i] + TT[k * d + i]);                      // :370-372
+      if (munc) {
+        double pk = 0.0;
+        for (int a = 0; a < nb; ++a) pk += hcf[(size_t)a * nxp + 1 + k] * hcf[(size_t)a * nxp + 1 + i];
+        d2s2 += 2.0 * varK * pk;
+      }
       d2sigdx2[k * d + i] = sg != 0.0 ? (d2s2 - 2.0 * dsigdx[k] * dsigdx[i]) / (2.0 * sg) : NAN;   // :375-378
     }
   return 0;

@@ -468,13 +468,17 @@ __device__ __forceinline__ void wave_tile_gemm(d4 (&acc)[4], const double* ga, i
 // B[k = 0][n = 0], k runs along contiguous memory, n strides by ldb (a block of L used untransposed by the backward
 // solve).  Same staging buffers / pipeline as wave_tile_gemm; only the B staging differs: 8 consecutive threads fetch
 // the 16 k of one n (128 contiguous bytes) and scatter them into the k-major LDS rows.
+// The 16-deep chunks of K are applied from the LAST to the first: the backward solve calls this once per batch of finished column
+// blocks, later batches holding lower k, so the order in which the products enter the accumulators is k-chunk-descending over the
+// whole contraction however the blocks happen to be batched -- the result does not depend on timing or on the number of workgroups.
 __device__ __forceinline__ void wave_tile_gemm_nn(d4 (&acc)[4], const double* ga, int lda, const double* gb, int ldb, int nchunk,
                                                   double* sA, double* sB, int w, int l15, int l4, int sp, int sk) {
   constexpr int KB = 16, SA = 80, BUF = KB * SA;
   const size_t a8 = (size_t)8 * lda;
   const int tid = threadIdx.x;
   const int bk = 2 * (tid & 7), bn = tid >> 3;               // B staging: k pair, n (and n + 32)
-  const double* gbt = gb + bk + (size_t)bn * ldb;
+  const double* gbt = gb + bk + (size_t)bn * ldb + (size_t)(nchunk - 1) * KB;
+  ga += (size_t)(nchunk - 1) * 2 * a8;
   const size_t bn32 = (size_t)32 * ldb;
   double2 ra0_a, ra0_b, rb0_a, rb0_b, ra1_a, ra1_b, rb1_a, rb1_b;
 #define GPG_NN_GLOAD(set)                                        \
@@ -482,8 +486,8 @@ __device__ __forceinline__ void wave_tile_gemm_nn(d4 (&acc)[4], const double* ga
   ra##set##_b = *reinterpret_cast<const double2*>(ga + a8);      \
   rb##set##_a = *reinterpret_cast<const double2*>(gbt);          \
   rb##set##_b = *reinterpret_cast<const double2*>(gbt + bn32);   \
-  ga += 2 * a8;                                                  \
-  gbt += KB;
+  ga -= 2 * a8;                                                  \
+  gbt -= KB;
 #define GPG_NN_SSTORE(buf, set)                                                              \
   {                                                                                          \
     double2 v0, v1;                                                                          \

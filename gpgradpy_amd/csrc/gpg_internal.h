@@ -16,6 +16,7 @@
 #define GPG_RHS_ROWS 128  // right-hand-side rows appended below the matrix (ride along the Cholesky)
 #define GPG_MAX_NBETA (GPG_MAX_DIM + 1)   // coefficients of the first-order mean: n_beta + 1 <= 18 right-hand-side rows are in use
 #define GPG_BETA_STRIDE 24                // doubles per slot of the coefficient vectors behind the reduction scalars
+#define GPG_MU_SMALL (2 * GPG_MAX_NBETA * GPG_MAX_NBETA + 8)   // mean-uncertainty state: H | its Cholesky factor | flag
 
 // Arguments of the fused assembly kernels (passed by value -> SGPRs / kernarg segment).
 struct AsmParams {
@@ -144,6 +145,16 @@ struct gpg_ctx {
   double* jbuf = nullptr;    // scratch of gpg_predict_joint: Gram partials | Kqq | difference tensor | cov | mean partials (on first use)
   size_t jbuf_bytes = 0;
   int gram_splits = 0;       // K-chunks of rows_gram_splitk_kernel (gpg_set_gram_splits; 0 = from the shape)
+  // uncertainty of the mean coefficients (meanunc.hip)
+  int mean_unc = 0;          // gpg_set_mean_uncertainty
+  bool mu_ready = false;     // mu_buf / mu_small belong to the posterior kept in set 1 (cleared by gpg_setup_eval*; only read while eval_ready)
+  double* mu_buf = nullptr;  // W_V = L^-1 P^-1 V | L^-T W_V, each [Npad x n_beta], the entries of a column contiguous (on first use)
+  size_t mu_buf_elems = 0;
+  double* mu_small = nullptr;   // [GPG_MU_SMALL] H = V' K^-1 V | R (H = R R^T) | flag (0, or 1 + the failing pivot)
+  double mu_host[GPG_MU_SMALL] = {0};   // host copy of mu_small
+  double* mu_scr = nullptr;  // per-call scratch: c' = R^-1 u | c = H^-1 u [n_beta x rows each] | q [rows] | K-chunk partials of Z W_V
+  size_t mu_scr_elems = 0;
+  double *mu_cf = nullptr, *mu_cb = nullptr, *mu_q = nullptr;   // into mu_scr, set by gpg_meanunc_rows
   double* batchA = nullptr;     // [batch_cap x A_elems] workspaces of the batched small-matrix factorisation (on first use)
   double* batchV = nullptr;     // [batch_cap x 3 x Npad] dvec / invp / dinv of each batched matrix
   int batch_cap = 0;
@@ -254,6 +265,12 @@ int gpg_with_fallback(gpg_ctx* c, const std::function<int()>& f);       // api.h
 int gpg_solve_failure(gpg_ctx* c);                                        // api.hip: -4 when *h_info reports a timed-out dataflow solve
 int gpg_predict_bufs(gpg_ctx* c, int nxp);                                // api.hip: Wt / xq_dev / musig / gradbuf for nxp query rows
 int gpg_ws_activate(gpg_ctx* c, int which);                              // make workspace set `which` the active one (allocates set 1 on first use)
+// meanunc.hip (all on the active workspace set 1; used only while gpg_ctx::mean_unc is on, and by gpg_mean_gram)
+int gpg_meanunc_ensure(gpg_ctx* c);                                       // per-model state (synchronises once when it has to build it)
+int gpg_meanunc_rows(gpg_ctx* c, const double* Z, int ldz, int m, int nx);   // after the forward sweep of m rows: mu_cf, mu_cb, mu_q
+void gpg_meanunc_update_rows(gpg_ctx* c, double* Z, int ldz, int nx);     // after the backward sweep: rows += c (K^-1 V)
+void gpg_meanunc_add_cov(gpg_ctx* c, int m, int mp, double varK, double* cov_dev);   // cov += varK C' C'^T
+void gpg_meanunc_free(gpg_ctx* c);
 
 // Device allocation inside a launch helper (task lists, flags, carrier tiles): on failure the pointer stays null, the
 // context is marked and the helper returns WITHOUT launching; the API call reports it (GPG_LAUNCH_OK) instead of a

@@ -274,6 +274,10 @@ int predict_joint_once(gpg_ctx* c, int nx, const double* xq, double varK, int wi
   GPG_HIP_OK(c, hipSetDevice(c->device));
   if (gpg_ws_activate(c, 1) != 0) return -2;
   if (int rc = gpg_predict_bufs(c, mp)) return rc;
+  const bool munc = c->mean_unc != 0 && cov != nullptr;   // uncertainty of the mean coefficients (meanunc.hip): cov += varK U H^-1 U^T
+  if (munc) {
+    if (int rc = gpg_meanunc_ensure(c)) return rc;
+  }
   const int Npad = c->Npad, ktiles = Npad / 64, T = mp / 64, ntiles = T * (T + 1) / 2;
   const int splits = gram_splits_for(mp, Npad, c->gram_splits);
   const int S = ktiles < kMeanSlicesMax ? ktiles : kMeanSlicesMax;    // slices of the mean reduction
@@ -323,6 +327,9 @@ int predict_joint_once(gpg_ctx* c, int nx, const double* xq, double varK, int wi
   }
   if (cov) {
     gpg_forward_rows(c, c->Wt, mp, mp, m);
+    if (munc) {
+      if (int rc = gpg_meanunc_rows(c, c->Wt, mp, m, nx)) return rc;
+    }
     hipLaunchKernelGGL(joint_qdiff_kernel, dim3((unsigned)(((long long)nx * nx + 255) / 256)), dim3(256), 0, c->stream, c->xq_dev, mp, nx, d,
                        rt, gpos);
     if (gpg_kern_rtensor_run(p.kernel, d, nx, nx, nx, nx, with_grad ? 1 : 0, p.theta, p.hp_kernel, rt, gpos, gpos, kqq, c->stream) != 0) {
@@ -331,6 +338,7 @@ int predict_joint_once(gpg_ctx* c, int nx, const double* xq, double varK, int wi
     }
     hipLaunchKernelGGL(rows_gram_splitk_kernel, dim3(ntiles, splits), dim3(256), 0, c->stream, c->Wt, mp, ktiles, splits, part);
     hipLaunchKernelGGL(gram_finish_kernel, dim3(ntiles, 16), dim3(256), 0, c->stream, part, ntiles, splits, kqq, m, varK, cov_dev);
+    if (munc) gpg_meanunc_add_cov(c, m, mp, varK, cov_dev);
     GPG_HIP_OK(c, hipMemcpyAsync(cov, cov_dev, sizeof(double) * (size_t)m * m, hipMemcpyDeviceToHost, c->stream));
   }
   GPG_HIP_OK(c, hipMemcpyAsync(c->h_info, c->info, sizeof(int), hipMemcpyDeviceToHost, c->stream));   // the dataflow sweep reports here

@@ -1224,10 +1224,33 @@ class GaussianProcess(HparaOptz):
             if calc_cond:                                 # GpEvalModel.py:39-41 -> Kernel.py:239-245 / 279-285
                 self.condK = self.calc_cond_device() if self.cond_norm == 2 else self.calc_cond_fro_device(hp)[0]
 
-    def eval_model(self, x2model_in, calc_grad=False, calc_hess=False, squeeze_nx=False):
-        """GpEvalModel.py:59-198: returns (mu, sig, dmudx, dsigdx, d2mudx2, d2sigdx2); the Hessians are
-        evaluated one point per call, as in the reference (GpEvalModel.py:358,369)."""
+    def _set_mean_unc(self, mean_unc):
+        """Switch of the device posterior (include/gpgrad.h: gpg_set_mean_uncertainty); every eval_* call sets it for itself."""
+        if mean_unc and self.b_use_data_scl:
+            raise Exception('mean_unc=True is not setup for cases where data must be rescaled')
+        rc = self._lib.gpg_set_mean_uncertainty(self._ctx, int(bool(mean_unc)))
+        if rc != 0:
+            raise _lib.GpgError(f'gpg_set_mean_uncertainty failed ({rc}): {self._err()}')
+
+    def calc_beta_cov(self):
+        """Covariance of the GLS mean coefficients of the model set up by setup_eval_model: varK (V' Kcov^-1 V)^-1
+        [n_beta, n_beta] (include/gpgrad.h: gpg_mean_gram gives the matrix in the brackets)."""
         assert self.KernEta_chofac is not None, 'To evaluate the surr the Cholesky decomposition is required'
+        if not self._eval_ready:
+            raise Exception('setup_eval_model() must be called (again): set_data() replaced the data of the device model')
+        nb = self.n_beta_coeff
+        H = np.empty((nb, nb))
+        rc = self._lib.gpg_mean_gram(self._ctx, _lib.as_dp(H))
+        if rc != 0:
+            raise _lib.GpgError(f'gpg_mean_gram failed ({rc}): {self._err()}')
+        return float(self.hp_vals.varK) * np.linalg.inv(H)
+
+    def eval_model(self, x2model_in, calc_grad=False, calc_hess=False, squeeze_nx=False, mean_unc=False):
+        """GpEvalModel.py:59-198: returns (mu, sig, dmudx, dsigdx, d2mudx2, d2sigdx2); the Hessians are
+        evaluated one point per call, as in the reference (GpEvalModel.py:358,369).  mean_unc=True: sig and its derivatives
+        include the uncertainty of the mean coefficients (gpg_set_mean_uncertainty); the default is the reference's posterior."""
+        assert self.KernEta_chofac is not None, 'To evaluate the surr the Cholesky decomposition is required'
+        self._set_mean_unc(mean_unc)
         if calc_hess:
             assert calc_grad, 'To return the hessian calc_grad must also be set to True'      # GpEvalModel.py:126-127
             if self.bvec_use_grad is not None and not np.all(self.bvec_use_grad):
@@ -1280,10 +1303,11 @@ class GaussianProcess(HparaOptz):
             return mu[0], sig[0], None, None, None, None
         return mu, sig, dmudx, dsigdx, d2mudx2, d2sigdx2
 
-    def eval_model_var(self, x2model_in, calc_grad=False, calc_hess=False, squeeze_nx=False):
+    def eval_model_var(self, x2model_in, calc_grad=False, calc_hess=False, squeeze_nx=False, mean_unc=False):
         """GpEvalModel.py:200-317: variance form of the posterior, returns (sig2, dsig2dx, d2sig2dx2) with
-        sig2 = varK (1 - diag(Kxy K^-1 Kyx)) and dsig2dx of calc_dsig2dx (:327-337)."""
+        sig2 = varK (1 - diag(Kxy K^-1 Kyx)) and dsig2dx of calc_dsig2dx (:327-337); mean_unc as in eval_model."""
         assert self.KernEta_chofac is not None, 'To evaluate the surr the Cholesky decomposition is required'
+        self._set_mean_unc(mean_unc)
         if x2model_in.ndim == 1:
             x2model = x2model_in[None, :]
         elif x2model_in.ndim == 2:
@@ -1315,12 +1339,14 @@ class GaussianProcess(HparaOptz):
             return sig2[0], (dsig2dx[0, :] if calc_grad else None), None
         return sig2, dsig2dx, None
 
-    def eval_model_joint(self, x2model_in, calc_grad=False):
+    def eval_model_joint(self, x2model_in, calc_grad=False, mean_unc=False):
         """Joint posterior of the latent function at the nx query points (include/gpgrad.h: gpg_predict_joint): returns
         (mean [m], cov [m, m]) with m = nx, or m = nx (dim + 1) with calc_grad: rows derivative-major like the training data,
         row blk * nx + j = f(x_j) for blk = 0 and d f / d x_(blk-1) at x_j otherwise.  cov = varK (Kqq - Kqy Kcov^-1 Kyq) is
-        exactly symmetric and not clipped; the uncertainty of the mean coefficients is not part of it (as in eval_model)."""
+        exactly symmetric and not clipped; the uncertainty of the mean coefficients is part of it only with mean_unc=True, which adds
+        varK U (V' Kcov^-1 V)^-1 U' (gpg_set_mean_uncertainty); the mean is the same either way."""
         assert self.KernEta_chofac is not None, 'To evaluate the surr the Cholesky decomposition is required'
+        self._set_mean_unc(mean_unc)
         if x2model_in.ndim == 1:
             x2model = x2model_in[None, :]
         elif x2model_in.ndim == 2:
@@ -1345,12 +1371,12 @@ class GaussianProcess(HparaOptz):
             raise _lib.GpgError(f'gpg_predict_joint failed ({rc}): {self._err()}')
         return mean, cov
 
-    def sample_posterior(self, x2model_in, n_samples, calc_grad=False, seed=None, z=None):
+    def sample_posterior(self, x2model_in, n_samples, calc_grad=False, seed=None, z=None, mean_unc=False):
         """Draws from the joint posterior at the query points: (f_samples [n_samples, nx], g_samples [n_samples, nx, dim] or
         None without calc_grad).  z: optional [n_samples, m] standard normals in the row order of eval_model_joint;
         otherwise np.random.default_rng(seed).standard_normal.  The covariance comes from the device, the draw itself is
-        host arithmetic (gpgradpy_amd/joint.py)."""
-        mean, cov = self.eval_model_joint(x2model_in, calc_grad=calc_grad)
+        host arithmetic (gpgradpy_amd/joint.py).  mean_unc=True: the draws carry the uncertainty of the mean coefficients too."""
+        mean, cov = self.eval_model_joint(x2model_in, calc_grad=calc_grad, mean_unc=mean_unc)
         m = mean.size
         nx = m // (self.dim + 1) if calc_grad else m
         if z is None:

@@ -101,8 +101,8 @@ int gpg_set_noise(gpg_ctx* ctx, const double* noise_var);
  *     counts as a failed factorisation in every respect: although the Cholesky factor of the matrix itself is good, the context
  *     marks it invalid (gpg_get_matrix 3 and gpg_factor_apply refuse until the next successful call).
  *   - gpg_predict* add the mean and its gradient: mu += beta_0 + xq . beta_1..d, dmudx += beta_1..d; d2mudx2 is unchanged (the
- *     Hessian of the mean is zero).  sig, dsigdx, d2sigdx2 and gpg_predict_var are unchanged: as in the reference, the posterior
- *     variance does NOT include the uncertainty of the mean coefficients.
+ *     Hessian of the mean is zero).  sig, dsigdx, d2sigdx2 and gpg_predict_var are unchanged by the mean order: as in the reference,
+ *     the posterior variance treats the mean coefficients as known unless gpg_set_mean_uncertainty switches their uncertainty in.
  *   - gpg_get_matrix, gpg_factor_apply, gpg_dcov_quadform, gpg_cond_fro, gpg_abs_rowsum and gpg_kern_* do not depend on the mean. */
 int gpg_set_mean_order(gpg_ctx* ctx, int order);
 
@@ -183,7 +183,8 @@ int gpg_setup_eval_mean(gpg_ctx* ctx, const gpg_hp* hp, const double* beta, doub
  * (GpEvalModel.py:133-139), K^-1 Kyx (GpEvalModel.py:154), mu = beta + Kyx' alpha (:168),
  * sig = sqrt(max(0, 1 - diag(Kxy K^-1 Kyx))) * sqrt(varK) (:162-166).  xq [nx, dim] row-major.
  * sig2_raw [nx] (may be NULL) receives the unclipped 1 - diag(...) that the reference asserts to be
- * non-negative (GpEvalModel.py:163). */
+ * non-negative (GpEvalModel.py:163).  As in the reference, sig treats the mean coefficients as known; with
+ * gpg_set_mean_uncertainty on, sig2_raw (and with it sig) gains u' (V' Kcov^-1 V)^-1 u of that switch. */
 int gpg_predict(gpg_ctx* ctx, int nx, const double* xq, double varK, double* mu, double* sig,
                 double* sig2_raw);
 
@@ -218,7 +219,8 @@ int gpg_predict_hess(gpg_ctx* ctx, const double* xq, double varK, double* mu, do
  *   model built without training gradients (use_grad = 0) and with_grad = 1.
  * Kcov: the matrix gpg_setup_eval factorised.
  * mean includes the mean function: beta_0 (+ xq . beta_1..d, and beta_k on the gradient rows, with mean order 1).
- * As in the reference, the uncertainty of the mean coefficients is NOT included.
+ * As in the reference, the mean coefficients count as known: cov does not hold their uncertainty unless gpg_set_mean_uncertainty is
+ * on, which adds varK U (V' Kcov^-1 V)^-1 U^T (exactly symmetric as well; mean is the same bits either way).
  * Not clipped: tiny negative diagonal entries are returned as computed.
  * mean or cov may be NULL.  m padded to a multiple of 64 must be <= 4096 (-1 beyond), and gpg_setup_eval must have succeeded (-1).
  * On the device: the cross-covariance rows of all points and blocks, one multi-row forward sweep Z = Kqy P^-1 L^-T, then
@@ -226,6 +228,28 @@ int gpg_predict_hess(gpg_ctx* ctx, const double* xq, double varK, double* mu, do
  * which also subtracts from Kqq and mirrors the tile): ordinary grids, no atomics, so the result is the same bits from run to
  * run and under any gpg_set_max_workgroups. */
 int gpg_predict_joint(gpg_ctx* ctx, int nx, const double* xq, double varK, int with_grad, double* mean, double* cov);
+
+/* Uncertainty of the GLS mean coefficients beta in the posterior (universal kriging; the reference has no counterpart: it treats beta
+ * as known).  on = 0 (default): every output is what it was without this switch, bit for bit.  on = 1: with
+ *   V [N, n_beta]  the augmented Vandermonde matrix of the model (gpg_set_mean_order),
+ *   H = V' Kcov^-1 V,  Kcov the matrix gpg_setup_eval factorised (varK := 1),
+ *   u_r = v_r - V' Kcov^-1 k_r,  k_r the cross-covariance column of query row r and v_r its mean basis: [1] or [1, x_j] on a value
+ *         row, 0 or e_(k+1) on the row of d/dx_k,
+ * the joint covariance becomes varK (Kqq - Kqy Kcov^-1 Kyq + U H^-1 U'), U [m, n_beta] = rows u_r, and
+ *   gpg_predict, gpg_predict_grad, gpg_predict_var, gpg_predict_hess: sig, sig2_raw, sig2, dsigdx, dsig2dx, d2sigdx2 are those of
+ *       sig2 = varK (1 - k' Kcov^-1 k + u' H^-1 u)  (sig = sqrt(max(0, .)), dsigdx = 0 where sig = 0, as without the switch);
+ *   gpg_predict_joint: cov gains varK U H^-1 U'.
+ * mu, dmudx, d2mudx2 and the joint mean do not change.  Callable before or after gpg_setup_eval*; values other than 0 / 1 return -1.
+ * Cost: W_V = L^-1 P^-1 V and K^-1 V (n_beta forward and backward rows, O(n_beta N^2)) once per gpg_setup_eval, by the first call
+ * that needs them; per query row one more pass over its swept row (O(n_beta N)).  If H is not positive definite (the pivot rule of
+ * the GLS solve: a pivot not above 1e-12 of its diagonal entry) the predict call returns -1 and names the pivot.  Ordinary grids,
+ * no atomics: the same bits from run to run and under any gpg_set_max_workgroups. */
+int gpg_set_mean_uncertainty(gpg_ctx* ctx, int on);
+
+/* H = V' Kcov^-1 V [n_beta, n_beta] (row-major, symmetric) of the posterior kept by gpg_setup_eval*: varK H^-1 is the covariance of
+ * the GLS coefficients.  Independent of gpg_set_mean_uncertainty.  -1 with a message before a successful gpg_setup_eval*, and -1
+ * with the pivot named if H is not positive definite by the rule above (H is written all the same). */
+int gpg_mean_gram(gpg_ctx* ctx, double* H);
 
 /* Number of K-chunks of the Gram kernel of gpg_predict_joint: 0 = automatic, a function of (m, N_pad) only -- never of the
  * device, the grid or gpg_set_max_workgroups; n >= 1: that many, capped at N_pad / 64.  Different chunk counts add the same
