@@ -23,7 +23,7 @@ ABI_SYMBOLS = (
     "gpg_setup_eval", "gpg_predict", "gpg_predict_grad", "gpg_predict_var", "gpg_predict_hess", "gpg_get_matrix", "gpg_kern_rtensor", "gpg_kern_rtensor_grad_hp", "gpg_kern_rtensor_hess_x", "gpg_factor_apply", "gpg_dcov_quadform", "gpg_cond_fro", "gpg_set_noise", "gpg_abs_rowsum", "gpg_set_gradient_nugget", "gpg_lkd_alpha", "gpg_prof_enable", "gpg_prof_read", "gpg_set_panel", "gpg_set_lookahead", "gpg_set_factor_mode", "gpg_set_pair_mode", "gpg_factor_fallbacks", "gpg_overlap_fallbacks", "gpg_solve_fallbacks", "gpg_last_factor", "gpg_set_batch", "gpg_reserve_batch", "gpg_set_max_workgroups",
     "gpg_device_info", "gpg_multi_create", "gpg_multi_destroy", "gpg_multi_last_error", "gpg_multi_count", "gpg_multi_set_data",
     "gpg_multi_lkd_batch", "gpg_set_mean_order", "gpg_lkd_beta", "gpg_setup_eval_mean", "gpg_multi_set_mean_order",
-    "gpg_predict_joint", "gpg_set_gram_splits", "gpg_set_mean_uncertainty", "gpg_mean_gram",
+    "gpg_predict_joint", "gpg_set_gram_splits", "gpg_set_mean_uncertainty", "gpg_mean_gram", "gpg_loo",
 )
 
 
@@ -100,6 +100,8 @@ def load():
     lib.gpg_set_mean_uncertainty.restype = C.c_int
     lib.gpg_mean_gram.argtypes = [vp, dp]
     lib.gpg_mean_gram.restype = C.c_int
+    lib.gpg_loo.argtypes = [vp, C.c_double, dp, dp, dp, dp, ip]
+    lib.gpg_loo.restype = C.c_int
     lib.gpg_get_matrix.argtypes = [vp, C.POINTER(GpgHp), C.c_int, dp]
     lib.gpg_get_matrix.restype = C.c_int
     lib.gpg_kern_rtensor.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp, C.c_double, C.c_int,

@@ -286,7 +286,7 @@ void gpg_destroy(gpg_ctx* c) {
                     c->ws[1].A, c->ws[1].dvec, c->ws[1].invp, c->ws[1].zvec, c->ws[1].tmpv, c->ws[1].dinv,
                     c->Xt, c->y, c->noise, c->scal, c->eval_beta_dev, c->Wt, c->xq_dev,
                     c->musig, c->gradbuf, c->dense_tmp, c->Wfull, c->Minv, c->gpartial, c->batchA, c->batchV, c->vec_rows, c->vec_x, c->apply_buf,
-                    c->batchW, c->batchM, c->batchZ, c->gres, c->Kbuf, c->Tbuf, c->jbuf};
+                    c->batchW, c->batchM, c->batchZ, c->gres, c->Kbuf, c->Tbuf, c->jbuf, c->loo_scr};
   for (double* b : bufs) if (b) (void)hipFree(b);
   gpg_meanunc_free(c);
   if (c->info) (void)hipFree(c->info);

@@ -697,16 +697,17 @@ void gpg_forward_rows(gpg_ctx* c, double* W, int ldw, int rows, int valid) {
 //   (2) Minv[0:k1, 0:k1] -= W[0:k1, k0:k1] W[0:k1, k0:k1]^T panel by panel with the trailing-update kernel
 //       (lower tiles only): another N^3/3.
 // Replaces adj_ln_detK = cho_solve(chofac, eye(N)) of the reference (CalcLkd.py:174,234).
+// Minv == nullptr: step (1) only (gpg_loo needs W and no more than the point-diagonal blocks of W W^T).
 void gpg_inverse_from_factor(gpg_ctx* c, double* W, double* Minv) {
   // dataflow schedule: W = L^-T and Minv = -W W^T as one launch each (128 x 128 tiles); the blocked sweeps below remain
   // for the blocked factor mode (A/B runs, fallback after a timed-out wait)
   if (c->chol_impl != 0 || c->tail_cols != 0) {
-    if (gpg_launch_tile128_inverse(c, W, Minv)) return;
+    if (Minv ? gpg_launch_tile128_inverse(c, W, Minv) : gpg_launch_tile128_trinv(c, W)) return;
   }
   const int ld = c->ld, Npad = c->Npad, NB = c->nb_outer, ldw = c->Npad;
   const double* A = c->A;
   gpg_launch_identity(c, W, ldw);
-  (void)hipMemsetAsync(Minv, 0, sizeof(double) * (size_t)ldw * Npad, c->stream);
+  if (Minv) (void)hipMemsetAsync(Minv, 0, sizeof(double) * (size_t)ldw * Npad, c->stream);
   for (int k0 = 0; k0 < Npad; k0 += NB) {
     const int k1 = (k0 + NB < Npad) ? k0 + NB : Npad;
     if (c->panel_impl == 1) {   // rows [j1, k1) of a column block are still zero when it is solved: harmless extra rows
@@ -725,6 +726,6 @@ void gpg_inverse_from_factor(gpg_ctx* c, double* W, double* Minv) {
     if (k1 < Npad)
       launch_gemm<128, 128>(c, W + (size_t)k1 * ldw, ldw, W + (size_t)k0 * ldw, ldw, A + (size_t)k1 + (size_t)k0 * ld, ld,
                             k1, Npad - k1, k1 - k0, 0);
-    launch_gemm_trailing(c, Minv, ldw, W + (size_t)k0 * ldw, ldw, W + (size_t)k0 * ldw, ldw, k1, k1, k1 - k0, 0);
+    if (Minv) launch_gemm_trailing(c, Minv, ldw, W + (size_t)k0 * ldw, ldw, W + (size_t)k0 * ldw, ldw, k1, k1, k1 - k0, 0);
   }
 }

@@ -526,6 +526,14 @@ bool gpg_overlap_inverse_wwt(gpg_ctx* c, int B, const double* Abase, size_t a_st
   return launch_tile128_inverse_batch(c, B, Abase, a_stride, dinv_base, d_stride, Wbase, Mbase, info_base, 2, c->keep_flags + chol64_nflag(c, B));
 }
 bool gpg_launch_tile128_inverse(gpg_ctx* c, double* W, double* Minv) { return launch_tile128_inverse(c, W, Minv); }
+// W = L^-T of the factor in c->A alone (phase 1 of the pair above, on c->stream with the context's own flag buffer)
+bool gpg_launch_tile128_trinv(gpg_ctx* c, double* W) {
+  const double np = (double)c->Npad;
+  gpg_prof_begin(c, GPG_PROF_TRSM, np * np * np / 3.0);
+  const bool ok = launch_tile128_inverse_batch(c, 1, c->A, 0, c->dinv, 0, W, nullptr, c->info, 1);
+  gpg_prof_end(c);
+  return ok;
+}
 // out_dev[0] = squared Frobenius norm of the symmetric N x N matrix whose lower triangle sits in M (leading dimension ld)
 void gpg_launch_frob_lower(gpg_ctx* c, const double* M, int ld, double* partial, double* out_dev) {
   hipLaunchKernelGGL(frob_lower_cols_kernel, dim3(c->N), dim3(256), 0, c->stream, M, ld, c->N, partial);

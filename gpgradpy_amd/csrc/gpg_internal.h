@@ -17,6 +17,7 @@
 #define GPG_MAX_NBETA (GPG_MAX_DIM + 1)   // coefficients of the first-order mean: n_beta + 1 <= 18 right-hand-side rows are in use
 #define GPG_BETA_STRIDE 24                // doubles per slot of the coefficient vectors behind the reduction scalars
 #define GPG_MU_SMALL (2 * GPG_MAX_NBETA * GPG_MAX_NBETA + 8)   // mean-uncertainty state: H | its Cholesky factor | flag
+#define GPG_MU_SMALL_R (GPG_MAX_NBETA * GPG_MAX_NBETA)         // offset of the factor R (lower, [n_beta x n_beta] row-major) in it
 
 // Arguments of the fused assembly kernels (passed by value -> SGPRs / kernarg segment).
 struct AsmParams {
@@ -155,6 +156,8 @@ struct gpg_ctx {
   double* mu_scr = nullptr;  // per-call scratch: c' = R^-1 u | c = H^-1 u [n_beta x rows each] | q [rows] | K-chunk partials of Z W_V
   size_t mu_scr_elems = 0;
   double *mu_cf = nullptr, *mu_cb = nullptr, *mu_q = nullptr;   // into mu_scr, set by gpg_meanunc_rows
+  double* loo_scr = nullptr; // per-call scratch of gpg_loo (loo.hip): K-chunk partials | prec | cov | resid | qy | H^-1 V' alpha | bad flags
+  size_t loo_scr_elems = 0;
   double* batchA = nullptr;     // [batch_cap x A_elems] workspaces of the batched small-matrix factorisation (on first use)
   double* batchV = nullptr;     // [batch_cap x 3 x Npad] dvec / invp / dinv of each batched matrix
   int batch_cap = 0;
@@ -228,6 +231,7 @@ void gpg_overlap_inverse_cancel(gpg_ctx* c);                // the overlapped fa
 bool gpg_overlap_inverse_wwt(gpg_ctx* c, int B, const double* Abase, size_t a_stride, const double* dinv_base, int d_stride, double* Wbase,
                              double* Mbase, int* info_base);   // Minv = -W W^T on the main stream, after W
 bool gpg_launch_tile128_inverse(gpg_ctx* c, double* W, double* Minv);   // Minv <- -(L L^T)^-1 by two dataflow launches
+bool gpg_launch_tile128_trinv(gpg_ctx* c, double* W);                   // W <- L^-T alone: the first of the two
 bool gpg_launch_tile128_inverse_batch(gpg_ctx* c, int B, const double* Abase, size_t a_stride, const double* dinv_base, int d_stride,
                                       double* Wbase, double* Mbase, int* info_base);   // the same for B factors at once
 void gpg_launch_frob_lower(gpg_ctx* c, const double* M, int ld, double* partial, double* out_dev);   // squared Frobenius norm (lower storage)
@@ -248,7 +252,7 @@ void gpg_launch_cross_grad(gpg_ctx* c, const AsmParams& p, int nx, int nxp, doub
 void gpg_launch_hess_stage(gpg_ctx* c, const AsmParams& p, int nxp, double* h1, double* h2, double* T, int stage);
 void gpg_launch_combine_rows(gpg_ctx* c, int slot);                       // RHS row 0 <- L^-1 P^-1 (y - V beta)
 void gpg_launch_identity(gpg_ctx* c, double* W, int ldw);
-void gpg_inverse_from_factor(gpg_ctx* c, double* W, double* Minv);       // Minv <- -(L L^T)^-1 (lower)
+void gpg_inverse_from_factor(gpg_ctx* c, double* W, double* Minv);       // Minv <- -(L L^T)^-1 (lower); Minv == nullptr: W = L^-T only
 void gpg_launch_grad_contract(gpg_ctx* c, const AsmParams& p, double* partial, double* out_dev, const double* zvec,
                               const double* Minv);
 void gpg_launch_unscale(gpg_ctx* c, const double* v, double* z);          // z = v / invp

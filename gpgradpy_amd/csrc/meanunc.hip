@@ -21,7 +21,7 @@ constexpr int kMuChunk = 256, kMuSlices = 4;
 constexpr double kMuPivTol = 1e-12;          // the pivot rule of lkd_reduce_lin_kernel
 constexpr int kMuWorkgroups = 512;           // (row tile, K-chunk) workgroups of mu_u_partial_kernel, about
 constexpr int kMuChunksMax = 64;             // at most this many K-chunks: one sum of mu_u_finish_kernel is two rounds of loads at most
-constexpr int kSmallH = 0, kSmallR = GPG_MAX_NBETA * GPG_MAX_NBETA, kSmallFlag = 2 * GPG_MAX_NBETA * GPG_MAX_NBETA;
+constexpr int kSmallH = 0, kSmallR = GPG_MU_SMALL_R, kSmallFlag = 2 * GPG_MAX_NBETA * GPG_MAX_NBETA;
 constexpr int kSmallCount = GPG_MU_SMALL;
 
 __device__ __forceinline__ void wave_lds_sync() {

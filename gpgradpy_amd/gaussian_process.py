@@ -18,6 +18,7 @@ from .hpara import HparaOptzInfo, HparaOptzVal, LkdInfo
 from .rescaling import Rescaling, calc_dist_min, calc_dist_max
 from .hpara_optz import HparaOptz
 from .joint import draw_from_joint
+from .loo import loo_by_point, loo_by_row, point_rows
 
 
 class DeviceChoFactor:
@@ -1389,6 +1390,40 @@ class GaussianProcess(HparaOptz):
         if not calc_grad:
             return s, None
         return s[:, :nx], np.transpose(s[:, nx:].reshape(-1, self.dim, nx), (0, 2, 1))
+
+    def loo_cv(self, mean_unc=False, by='point'):
+        """Leave-one-out cross-validation of the model set up by setup_eval_model, without a refit (include/gpgrad.h: gpg_loo;
+        the host arithmetic is gpgradpy_amd/loo.py).  by='point' leaves out a point with its gradient: the result has mu_f [n],
+        mu_g [n, dim] (the predictions from all other points; NaN where a point has no gradient), resid_f, resid_g (data minus
+        prediction), cov [n, bs, bs] of the prediction of the observed rows (bs = dim + 1 with gradients), z (whitened
+        residuals), ln_pseudo_lkd_pt [n], their sum ln_pseudo_lkd and n_bad.  by='row' leaves every data row out alone: mu,
+        resid, var, z, ln_pseudo_lkd_row [n_data] in data_vec order, ln_pseudo_lkd, n_bad.  mean_unc=True: the mean
+        coefficients are re-estimated without the left-out data (universal kriging); the default keeps them fixed."""
+        assert self.KernEta_chofac is not None, 'To evaluate the surr the Cholesky decomposition is required'
+        if by not in ('point', 'row'):
+            raise ValueError(f"by must be 'point' or 'row', got {by!r}")
+        self._set_mean_unc(mean_unc)
+        if (self.hp_vals == self._hp_vals_model_setup) is False:
+            raise Exception('Cannot change hp_vals between calling setup_eval_model() and eval_model()')
+        if self.b_use_data_scl:
+            raise Exception('The method loo_cv() is not setup for cases where data must be rescaled')
+        if not self._eval_ready:
+            raise Exception('setup_eval_model() must be called (again): set_data() replaced the data of the device model')
+        n, N = self.n_eval, self.n_data
+        bs = self.dim + 1 if self.use_grad else 1
+        resid, qy = np.empty(N), np.empty(N)
+        cov, prec = np.empty((n, bs, bs)), np.empty((n, bs, bs))
+        n_bad = C.c_int(0)
+        varK = float(self.hp_vals.varK)
+        rc = self._lib.gpg_loo(self._ctx, varK, _lib.as_dp(resid), _lib.as_dp(cov), _lib.as_dp(prec), _lib.as_dp(qy), C.byref(n_bad))
+        if rc != 0:
+            raise _lib.GpgError(f'gpg_loo failed ({rc}): {self._err()}')
+        rows = point_rows(n, self.dim, bool(self.use_grad), self.bvec_use_grad)
+        if by == 'row':
+            return loo_by_row(self.data_vec, rows, prec, qy, varK)
+        res = loo_by_point(self.data_vec, rows, resid, cov)
+        assert res.n_bad >= n_bad.value
+        return res
 
     def set_gram_splits(self, n):
         """K-chunks of the Gram kernel behind eval_model_joint (include/gpgrad.h: gpg_set_gram_splits; 0 = from the shape)."""

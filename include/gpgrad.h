@@ -251,6 +251,29 @@ int gpg_set_mean_uncertainty(gpg_ctx* ctx, int on);
  * with the pivot named if H is not positive definite by the rule above (H is written all the same). */
 int gpg_mean_gram(gpg_ctx* ctx, double* H);
 
+/* Leave-one-out cross-validation of the posterior kept by gpg_setup_eval*, point by point and without a refit (the reference has
+ * no counterpart).  The unit left out is the point: its value row a and, if it carries a gradient, its rows n + k ng + gpos[a],
+ * k = 0..dim-1 (the row layout of gpg_set_data; gpg_set_grad_mask honoured).  bs = dim + 1 with use_grad, else 1.  With
+ *   B = Kcov^-1, Kcov the matrix gpg_setup_eval factorised (varK := 1, noise and nugget included), alpha = Kcov^-1 (y - V beta):
+ *   prec  [n, bs, bs] row-major, exactly symmetric: the block of B on the rows of point a; with gpg_set_mean_uncertainty on the
+ *         block of Q = B - B V (V' B V)^-1 V' B (the mean coefficients are re-estimated without the point: Dubrule's formulas).
+ *         A point without gradient rows has entry [0, 0] only, the rest of its block is 0.0.
+ *   qy    [N]: alpha, the same bits as alpha_out of gpg_setup_eval*; with the switch on Q y = alpha - B V (V' B V)^-1 V' alpha
+ *         (the correction is formed even though it vanishes in exact arithmetic when beta is the GLS optimum).
+ *   resid [N] in data_vec order: on the rows of a, prec_a^-1 qy_a = the observed data minus their prediction from all other points.
+ *   cov   [n, bs, bs] = varK prec_a^-1, exactly symmetric, laid out as prec: the covariance of that prediction of the OBSERVED rows
+ *         (noise and nugget are part of it).
+ * Each block is inverted through its Cholesky factor on the device, with the pivot rule of the GLS solve: a pivot not above
+ * 1e-12 of the diagonal entry it started from marks the block bad -- NaN in that point's resid and cov; *n_bad counts the bad
+ * blocks and the call still returns 0.  Any output pointer may be NULL.  -1 with a message before a successful gpg_setup_eval*;
+ * with mean uncertainty on, -1 naming the pivot if V' B V is not positive definite; -2 out of memory.
+ * On the device: W = L^-T by the one-launch dataflow sweep of the gradient path (N^3/3 flops), then only the n point-diagonal
+ * blocks of W W^T -- one pass over the upper triangle of W (4 N^2 bytes, N^2 (dim + 2) / 2 flops) instead of the second N^3/3
+ * sweep behind the full inverse -- as K-chunk partials added in chunk order, and one thread per point for the block algebra.
+ * Ordinary grids, no atomics: the same bits from run to run and under any gpg_set_max_workgroups.  Likelihood-side state
+ * (gpg_lkd*, gpg_cond_fro) is neither read nor invalidated. */
+int gpg_loo(gpg_ctx* ctx, double varK, double* resid, double* cov, double* prec, double* qy, int* n_bad);
+
 /* Number of K-chunks of the Gram kernel of gpg_predict_joint: 0 = automatic, a function of (m, N_pad) only -- never of the
  * device, the grid or gpg_set_max_workgroups; n >= 1: that many, capped at N_pad / 64.  Different chunk counts add the same
  * products in a different order: results agree to rounding, not bitwise. */
