@@ -274,9 +274,10 @@ def calc_lkd(X, y, theta, kernel, use_grad, wellcond, etaK, noise_vec, noisy, va
     return LkdResult(True, beta, varK_opt, ln_det, -(N * np.log(varK_opt) + ln_det) / 2.0, alpha, fac)
 
 
-def _kcov_only(X, theta, kernel, use_grad, wellcond, etaK, n, d, noise_fun, varK):
-    """Regularised covariance as a function of the hyperparameters (no factorisation)."""
-    Kern = kern_grad(X, X, theta, kernel) if use_grad else kern_base(X, X, theta, kernel)
+def _kcov_only(X, theta, kernel, use_grad, wellcond, etaK, n, d, noise_fun, varK, grad_mask=None):
+    """Regularised covariance as a function of the hyperparameters (no factorisation).  grad_mask = bvec_use_grad of the
+    training points (rows and columns of the points it leaves out are dropped; noise_fun gives the vector of that length)."""
+    Kern = kern_grad(X, X, theta, kernel, mask1=grad_mask, mask2=grad_mask) if use_grad else kern_base(X, X, theta, kernel)
     Kw = Kern + np.diag(noise_fun() / varK)
     if wellcond == "precon":
         return varK * (Kw + etaK * np.diag(np.diag(Kw)))       # = P (Kcor + eta I) P, Kernel.py:227-237
@@ -284,52 +285,64 @@ def _kcov_only(X, theta, kernel, use_grad, wellcond, etaK, n, d, noise_fun, varK
 
 
 def calc_lkd_grad(X, y, theta, kernel, use_grad, wellcond, etaK, std_f, std_g, noisy, varK=None,
-                  var_fval=None, var_fgrad=None, rel_step=1e-6):
+                  var_fval=None, var_fgrad=None, rel_step=1e-6, grad_mask=None, return_parts=False, rel_step_var=None):
     """d ln_lkd / d hp by the adjoint formula of the reference (CalcLkd.py:170-177 noise-free, :230-235 noisy)
     with the derivative tensor d Kcov / d hp_k (GpHparaGrad.py:13-155) replaced by central differences of the
     covariance matrix itself (rel. step 1e-6: truncation ~1e-12, rounding ~1e-10 relative per entry).
-    Returns the vector ordered [theta(d), alpha? (RatQu), varK?, var_fval?, var_fgrad?] like HparaOptzInfo."""
+    Returns the vector ordered [theta(d), alpha? (RatQu), varK?, var_fval?, var_fgrad?] like HparaOptzInfo.
+
+    grad_mask = bvec_use_grad (y, std_g hold the rows of the points it keeps); the reference itself fails there, the mask handling
+    is that of calc_lkd, which the mask fixtures pin.
+    return_parts=True: (alpha' G_k alpha, -1/2 tr(Kcov^-1 G_k)) per slot in the same order -- g_aa[k] and g_inv[k] of gpg_lkd_grad
+    (include/gpgrad.h); the gradient is s * first + second with s = 1/2 (noisy) or 1 / (2 varK) (noise-free).
+    rel_step_var: the step of the varK, var_fval and var_fgrad slots (default: rel_step).  The covariance is linear in these
+    three, so their central difference is exact at any step, and a small one only loses digits: the entries it subtracts are
+    O(varK), so with var_fval = 1e-4 and rel_step = 1e-6 the quotient carries eps varK / (2e-10) ~ 5e-7 relative error."""
     n, d = X.shape
-    nv = lambda vf=var_fval, vg=var_fgrad: calc_noise_vec(n, d, use_grad, std_f, std_g, vf, vg)
+    rsv = rel_step if rel_step_var is None else rel_step_var
+    ng = None if grad_mask is None else int(np.sum(grad_mask))
+    nv = lambda vf=var_fval, vg=var_fgrad: calc_noise_vec(n, d, use_grad, std_f, std_g, vf, vg, n_grad=ng)
     vK = varK if noisy else 1.0
-    r0 = calc_lkd(X, y, theta, kernel, use_grad, wellcond, etaK, nv(), noisy, varK=varK)
+    r0 = calc_lkd(X, y, theta, kernel, use_grad, wellcond, etaK, nv(), noisy, varK=varK, grad_mask=grad_mask)
     N = y.size
     Kinv = cho_solve(r0.factor.chofac, np.eye(N))
     al = r0.alpha
     Lam = (0.5 if noisy else 1.0 / (2.0 * r0.hp_varK)) * np.outer(al, al) - 0.5 * Kinv
-    out = []
+    out, out_aa, out_inv = [], [], []
 
-    def dcov(f_plus, f_minus, h):
-        return (f_plus - f_minus) / (2.0 * h)
+    def kcov(th, kern, noise_fun, vk):
+        return _kcov_only(X, th, kern, use_grad, wellcond, etaK, n, d, noise_fun, vk, grad_mask)
+
+    def add(f_plus, f_minus, h):
+        G = (f_plus - f_minus) / (2.0 * h)
+        if return_parts:
+            out_aa.append(al @ G @ al)
+            out_inv.append(-0.5 * np.sum(G * Kinv))
+        else:
+            out.append(np.sum(G * Lam))
     for k in range(d):
         h = rel_step * theta[k]
         tp, tm = theta.copy(), theta.copy()
         tp[k] += h
         tm[k] -= h
-        G = dcov(_kcov_only(X, tp, kernel, use_grad, wellcond, etaK, n, d, nv, vK),
-                 _kcov_only(X, tm, kernel, use_grad, wellcond, etaK, n, d, nv, vK), h)
-        out.append(np.sum(G * Lam))
+        add(kcov(tp, kernel, nv, vK), kcov(tm, kernel, nv, vK), h)
     kname, alpha = _kern_split(kernel)
     if kname == "RatQu":                       # the kernel's own hyperparameter sits between theta and varK (GpHparaOptz.py:90-96)
         h = rel_step * alpha
-        G = dcov(_kcov_only(X, theta, (kname, alpha + h), use_grad, wellcond, etaK, n, d, nv, vK),
-                 _kcov_only(X, theta, (kname, alpha - h), use_grad, wellcond, etaK, n, d, nv, vK), h)
-        out.append(np.sum(G * Lam))
+        add(kcov(theta, (kname, alpha + h), nv, vK), kcov(theta, (kname, alpha - h), nv, vK), h)
     if noisy:
-        h = rel_step * varK
-        G = dcov(_kcov_only(X, theta, kernel, use_grad, wellcond, etaK, n, d, nv, varK + h),
-                 _kcov_only(X, theta, kernel, use_grad, wellcond, etaK, n, d, nv, varK - h), h)
-        out.append(np.sum(G * Lam))
+        h = rsv * varK
+        add(kcov(theta, kernel, nv, varK + h), kcov(theta, kernel, nv, varK - h), h)
         if std_f is None:
-            h = rel_step * var_fval
-            G = dcov(_kcov_only(X, theta, kernel, use_grad, wellcond, etaK, n, d, lambda: nv(var_fval + h, var_fgrad), varK),
-                     _kcov_only(X, theta, kernel, use_grad, wellcond, etaK, n, d, lambda: nv(var_fval - h, var_fgrad), varK), h)
-            out.append(np.sum(G * Lam))
+            h = rsv * var_fval
+            add(kcov(theta, kernel, lambda: nv(var_fval + h, var_fgrad), varK),
+                kcov(theta, kernel, lambda: nv(var_fval - h, var_fgrad), varK), h)
         if use_grad and std_g is None:
-            h = rel_step * var_fgrad
-            G = dcov(_kcov_only(X, theta, kernel, use_grad, wellcond, etaK, n, d, lambda: nv(var_fval, var_fgrad + h), varK),
-                     _kcov_only(X, theta, kernel, use_grad, wellcond, etaK, n, d, lambda: nv(var_fval, var_fgrad - h), varK), h)
-            out.append(np.sum(G * Lam))
+            h = rsv * var_fgrad
+            add(kcov(theta, kernel, lambda: nv(var_fval, var_fgrad + h), varK),
+                kcov(theta, kernel, lambda: nv(var_fval, var_fgrad - h), varK), h)
+    if return_parts:
+        return np.array(out_aa), np.array(out_inv)
     return np.array(out)
 
 
@@ -382,10 +395,12 @@ def eval_model_grad(m: EvalModel, xq):
     return mu, sig, dmudx, dsigdx
 
 
-def kern_hess_x(x, Y, theta, kernel, use_grad):
+def kern_hess_x(x, Y, theta, kernel, use_grad, grad_mask=None):
     """Second derivatives of the cross-covariance row K(x, [Y, dY]) with respect to the query point x:
     [d, d, N] -- reference KernelSqExp.py:48-88 (base columns), :412-468 (gradient columns),
-    KernelMatern5f2.py:54-94, :453-530; r = x - y as in calc_Rtensor(x2model, x_eval)."""
+    KernelMatern5f2.py:54-94, :453-530; r = x - y as in calc_Rtensor(x2model, x_eval).
+    grad_mask = bvec_use_grad of the training points Y: the gradient columns of the points it leaves out are dropped
+    (_mask_index; the reference's own arrays do not fit together there, KernelSqExp.py:451-452).  N = n + n_grad d then."""
     x = np.asarray(x, dtype=float).ravel()
     n, d = Y.shape
     R = x[None, :] - Y                                   # [n, d]
@@ -433,21 +448,24 @@ def kern_hess_x(x, Y, theta, kernel, use_grad):
                                                         - np.sqrt(5) * inv_nu * Rt[:, i] * Rt[:, j] * Rt[:, k]) * base
     else:
         raise ValueError(kernel)
+    if use_grad and grad_mask is not None:
+        H = np.ascontiguousarray(H[:, :, _mask_index(n, d, grad_mask)])     # (the layout of the unmasked array)
     return H
 
 
 def eval_model_hess(m: EvalModel, xq):
     """(mu, sig, dmudx, dsigdx, d2mudx2, d2sigdx2) at ONE point -- reference GpEvalModel.py:59-198 with
-    calc_hess=True (:148-150, :176-178), calc_d2mudx2 :355-363, calc_d2sigdx2 :365-380.  No gradient masks."""
+    calc_hess=True (:148-150, :176-178), calc_d2mudx2 :355-363, calc_d2sigdx2 :365-380.  A training-side
+    gradient mask (m.grad_mask) selects the rows of the cross-covariance and the columns of kern_hess_x as everywhere else."""
     xq = np.atleast_2d(np.asarray(xq, dtype=float))
-    assert xq.shape[0] == 1 and m.grad_mask is None
+    assert xq.shape[0] == 1
     mu, sig, dmudx, dsigdx = eval_model_grad(m, xq)
     d = xq.shape[1]
-    Kg = kern_grad(m.X, xq, m.theta, m.kernel, grad_cols=True)
+    Kg = kern_grad(m.X, xq, m.theta, m.kernel, grad_cols=True, mask1=m.grad_mask if m.use_grad else None)
     if not m.use_grad:
         Kg = Kg[:m.X.shape[0], :]
     Kyx, dKxy_dx = Kg[:, :1], Kg[:, 1:].T
-    H = kern_hess_x(xq[0], m.X, m.theta, m.kernel, m.use_grad)
+    H = kern_hess_x(xq[0], m.X, m.theta, m.kernel, m.use_grad, m.grad_mask)
     sol = cho_solve(m.chofac, Kyx)                                        # K^-1 Kyx  [N, 1]
     d2mudx2 = H @ m.alpha
     term1 = H @ sol[:, 0]
