@@ -24,6 +24,7 @@ ABI_SYMBOLS = (
     "gpg_device_info", "gpg_multi_create", "gpg_multi_destroy", "gpg_multi_last_error", "gpg_multi_count", "gpg_multi_set_data",
     "gpg_multi_lkd_batch", "gpg_set_mean_order", "gpg_lkd_beta", "gpg_setup_eval_mean", "gpg_multi_set_mean_order",
     "gpg_predict_joint", "gpg_set_gram_splits", "gpg_set_mean_uncertainty", "gpg_mean_gram", "gpg_loo",
+    "gpg_set_fuse_max_tiles", "gpg_set_task_order",
 )
 
 
@@ -145,6 +146,9 @@ def load():
     lib.gpg_factor_fallbacks.restype = C.c_int
     lib.gpg_set_pair_mode.argtypes = [vp, C.c_int]
     lib.gpg_set_pair_mode.restype = C.c_int
+    for name in ("gpg_set_fuse_max_tiles", "gpg_set_task_order"):
+        getattr(lib, name).argtypes = [vp, C.c_int]
+        getattr(lib, name).restype = C.c_int
     for name in ("gpg_overlap_fallbacks", "gpg_solve_fallbacks"):
         getattr(lib, name).argtypes = [vp]
         getattr(lib, name).restype = C.c_int

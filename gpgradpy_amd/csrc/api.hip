@@ -1534,6 +1534,20 @@ int gpg_set_max_workgroups(gpg_ctx* c, int n) {
   return 0;
 }
 
+int gpg_set_fuse_max_tiles(gpg_ctx* c, int n) {
+  if (!c) return -1;
+  if (n < 0) { c->err = "fuse_max_tiles must be >= 0 (0 = never fuse)"; return -1; }
+  c->fuse_subdiag_max_tiles = n;
+  return 0;
+}
+
+int gpg_set_task_order(gpg_ctx* c, int order) {
+  if (!c) return -1;
+  if (order < -1 || order > 1) { c->err = "task order must be -1 (measured choice), 0 or 1"; return -1; }
+  c->task_order = order;
+  return 0;
+}
+
 int gpg_set_lookahead(gpg_ctx* c, int on) {
   if (!c) return -1;
   c->lookahead = (on & 1) ? 1 : 0;

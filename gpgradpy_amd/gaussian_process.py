@@ -1507,6 +1507,20 @@ class GaussianProcess(HparaOptz):
         if rc != 0:
             raise _lib.GpgError(f'gpg_set_max_workgroups failed ({rc}): {self._err()}')
 
+    def set_fuse_max_tiles(self, n):
+        """Diagnostic: a single matrix on 64-tiles fuses its sub-diagonal tiles into the diagonal tasks up to n tile columns
+        (include/gpgrad.h: gpg_set_fuse_max_tiles; 0 = never, default 48)."""
+        rc = self._lib.gpg_set_fuse_max_tiles(self._ctx, int(n))
+        if rc != 0:
+            raise _lib.GpgError(f'gpg_set_fuse_max_tiles failed ({rc}): {self._err()}')
+
+    def set_task_order(self, order):
+        """Diagnostic: ticket order of the dataflow factorisation (include/gpgrad.h: gpg_set_task_order; 0 column by column,
+        1 critical path first, -1 = default, the measured choice)."""
+        rc = self._lib.gpg_set_task_order(self._ctx, int(order))
+        if rc != 0:
+            raise _lib.GpgError(f'gpg_set_task_order failed ({rc}): {self._err()}')
+
     def reserve_batch(self, rows):
         """Allocate the workspaces calc_lkd_batch(rows) will use (setup, like set_data)."""
         rc = self._lib.gpg_reserve_batch(self._ctx, int(rows))

@@ -422,6 +422,16 @@ int gpg_set_pair_mode(gpg_ctx* ctx, int mode);
  * leave part of the device to another tenant. */
 int gpg_set_max_workgroups(gpg_ctx* ctx, int n);
 
+/* Diagnostic switches of the dataflow factorisation (tests/test_gpu_factor.py reaches every schedule at small sizes with them).  With
+ * the tile size and the fuse setting fixed the factor is the same bits under either task order.
+ * gpg_set_fuse_max_tiles: a single matrix on 64 x 64 tiles lets each diagonal task also compute the sub-diagonal tile below the previous
+ * diagonal tile ("fused") while the matrix has at most n 64-column tile columns; n >= 0, 0 = never fuse, default 48 (-1 if n < 0).
+ * gpg_set_task_order: ticket order of the factorisation's tasks -- 0 tile column by tile column, 1 critical path first (the next diagonal
+ * tile ahead of the rest of its column), -1 (default) the measured choice: 1 for batched launches and below 16384 padded columns, 0
+ * above; any other value returns -1 with an error text. */
+int gpg_set_fuse_max_tiles(gpg_ctx* ctx, int n);
+int gpg_set_task_order(gpg_ctx* ctx, int order);
+
 /* gpg_lkd_batch: up to max_matrices restart rows are assembled into separate workspaces and factorised by ONE
  * dataflow launch (task lists interleaved tile column by tile column).  A single small factorisation is
  * latency-bound and leaves most of the chip idle; a large one does so at its two ends.  Results are bit-identical to
