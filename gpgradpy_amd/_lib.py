@@ -24,7 +24,7 @@ ABI_SYMBOLS = (
     "gpg_device_info", "gpg_multi_create", "gpg_multi_destroy", "gpg_multi_last_error", "gpg_multi_count", "gpg_multi_set_data",
     "gpg_multi_lkd_batch", "gpg_set_mean_order", "gpg_lkd_beta", "gpg_setup_eval_mean", "gpg_multi_set_mean_order",
     "gpg_predict_joint", "gpg_set_gram_splits", "gpg_set_mean_uncertainty", "gpg_mean_gram", "gpg_loo",
-    "gpg_set_fuse_max_tiles", "gpg_set_task_order",
+    "gpg_set_fuse_max_tiles", "gpg_set_task_order", "gpg_predict_second", "gpg_set_second_chunk",
 )
 
 
@@ -97,6 +97,10 @@ def load():
     lib.gpg_predict_joint.restype = C.c_int
     lib.gpg_set_gram_splits.argtypes = [vp, C.c_int]
     lib.gpg_set_gram_splits.restype = C.c_int
+    lib.gpg_predict_second.argtypes = [vp, C.c_int, dp, C.c_double, dp, dp, dp, dp, dp]
+    lib.gpg_predict_second.restype = C.c_int
+    lib.gpg_set_second_chunk.argtypes = [vp, C.c_int]
+    lib.gpg_set_second_chunk.restype = C.c_int
     lib.gpg_set_mean_uncertainty.argtypes = [vp, C.c_int]
     lib.gpg_set_mean_uncertainty.restype = C.c_int
     lib.gpg_mean_gram.argtypes = [vp, dp]

@@ -145,7 +145,8 @@ struct gpg_ctx {
   int xq_cap = 0;
   double* jbuf = nullptr;    // scratch of gpg_predict_joint: Gram partials | Kqq | difference tensor | cov | mean partials (on first use)
   size_t jbuf_bytes = 0;
-  int gram_splits = 0;       // K-chunks of rows_gram_splitk_kernel (gpg_set_gram_splits; 0 = from the shape)
+  int gram_splits = 0;       // K-chunks of rows_gram_splitk_kernel and second_gram_kernel (gpg_set_gram_splits; 0 = from the shape)
+  int second_chunk = 0;      // query points per chunk of gpg_predict_second (gpg_set_second_chunk; 0 = from the dimension); jbuf is its scratch too
   // uncertainty of the mean coefficients (meanunc.hip)
   int mean_unc = 0;          // gpg_set_mean_uncertainty
   bool mu_ready = false;     // mu_buf / mu_small belong to the posterior kept in set 1 (cleared by gpg_setup_eval*; only read while eval_ready)
@@ -269,6 +270,10 @@ int gpg_with_fallback(gpg_ctx* c, const std::function<int()>& f);       // api.h
 int gpg_solve_failure(gpg_ctx* c);                                        // api.hip: -4 when *h_info reports a timed-out dataflow solve
 int gpg_predict_bufs(gpg_ctx* c, int nxp);                                // api.hip: Wt / xq_dev / musig / gradbuf for nxp query rows
 int gpg_ws_activate(gpg_ctx* c, int which);                              // make workspace set `which` the active one (allocates set 1 on first use)
+// joint.hip: the first steps of the joint posterior, shared with second.hip
+void gpg_launch_cross_joint(gpg_ctx* c, const AsmParams& p, int nx, int qblk, int mp);   // Wt <- rows of Kqy P^-1 (row r = blk * nx + j, leading dimension mp)
+int gpg_joint_mean_slices(const gpg_ctx* c);                                            // mpart below: this many times mp doubles
+void gpg_launch_joint_mean(gpg_ctx* c, int mp, int m, int nx, double* mpart, double* mean_dev);   // mean of those m rows, before they are swept
 // meanunc.hip (all on the active workspace set 1; used only while gpg_ctx::mean_unc is on, and by gpg_mean_gram)
 int gpg_meanunc_ensure(gpg_ctx* c);                                       // per-model state (synchronises once when it has to build it)
 int gpg_meanunc_rows(gpg_ctx* c, const double* Z, int ldz, int m, int nx);   // after the forward sweep of m rows: mu_cf, mu_cb, mu_q

@@ -260,6 +260,32 @@ int gram_splits_for(int mp, int Npad, int requested) {
 
 size_t round256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 
+}  // namespace
+
+// The rows of Kqy P^-1 of nx query points (xq_dev [d x mp]) into Wt, qblk = 1 (values) or d + 1 (values and derivatives) blocks
+void gpg_launch_cross_joint(gpg_ctx* c, const AsmParams& p, int nx, int qblk, int mp) {
+  if (p.kernel == GPG_KERNEL_SQEXP) launch_cross_joint_d<GPG_KERNEL_SQEXP>(c, p, nx, qblk, mp);
+  else if (p.kernel == GPG_KERNEL_RATQU) launch_cross_joint_d<GPG_KERNEL_RATQU>(c, p, nx, qblk, mp);
+  else launch_cross_joint_d<GPG_KERNEL_MA5F2>(c, p, nx, qblk, mp);
+}
+
+// slices of the mean reduction: mpart of gpg_launch_joint_mean holds this many times mp doubles
+int gpg_joint_mean_slices(const gpg_ctx* c) {
+  const int ktiles = c->Npad / 64;
+  return ktiles < kMeanSlicesMax ? ktiles : kMeanSlicesMax;
+}
+
+// mean_dev[r] = prior mean + (Kqy P^-1)[r, :] (p * alpha) for the m rows that gpg_launch_cross_joint left in Wt (before the sweep)
+void gpg_launch_joint_mean(gpg_ctx* c, int mp, int m, int nx, double* mpart, double* mean_dev) {
+  const int S = gpg_joint_mean_slices(c);
+  const int chunk = (c->N + S - 1) / S;
+  hipLaunchKernelGGL(joint_mean_partial_kernel, dim3(mp / 64, S), dim3(1024), 0, c->stream, c->Wt, mp, c->N, chunk, c->zvec, mpart);
+  hipLaunchKernelGGL(joint_mean_final_kernel, dim3((m + 255) / 256), dim3(256), 0, c->stream, mpart, mp, m, nx, S, c->eval_beta,
+                     c->eval_linear ? c->eval_beta_dev : (const double*)nullptr, c->xq_dev, c->d, mean_dev);
+}
+
+namespace {
+
 int predict_joint_once(gpg_ctx* c, int nx, const double* xq, double varK, int with_grad, double* mean, double* cov) {
   if (!c) return -1;
   if (!c->eval_ready) { c->err = "gpg_setup_eval must succeed before gpg_predict_joint"; return -1; }
@@ -280,7 +306,7 @@ int predict_joint_once(gpg_ctx* c, int nx, const double* xq, double varK, int wi
   }
   const int Npad = c->Npad, ktiles = Npad / 64, T = mp / 64, ntiles = T * (T + 1) / 2;
   const int splits = gram_splits_for(mp, Npad, c->gram_splits);
-  const int S = ktiles < kMeanSlicesMax ? ktiles : kMeanSlicesMax;    // slices of the mean reduction
+  const int S = gpg_joint_mean_slices(c);
   // scratch: Gram partials | Kqq | cov | difference tensor | mean partials | mean | gradient positions
   const size_t b_part = cov ? round256(sizeof(double) * (size_t)splits * ntiles * 4096) : 0;
   const size_t b_mm = cov ? round256(sizeof(double) * (size_t)m * m) : 0;
@@ -315,14 +341,9 @@ int predict_joint_once(gpg_ctx* c, int nx, const double* xq, double varK, int wi
   GPG_HIP_OK(c, hipMemsetAsync(c->Wt, 0, sizeof(double) * (size_t)mp * Npad, c->stream));
   GPG_HIP_OK(c, hipMemsetAsync(c->info, 0, sizeof(int), c->stream));
   const AsmParams p = c->eval_params;
-  if (p.kernel == GPG_KERNEL_SQEXP) launch_cross_joint_d<GPG_KERNEL_SQEXP>(c, p, nx, qblk, mp);
-  else if (p.kernel == GPG_KERNEL_RATQU) launch_cross_joint_d<GPG_KERNEL_RATQU>(c, p, nx, qblk, mp);
-  else launch_cross_joint_d<GPG_KERNEL_MA5F2>(c, p, nx, qblk, mp);
+  gpg_launch_cross_joint(c, p, nx, qblk, mp);
   if (mean) {   // before the sweep: mean = prior + (Kqy P^-1) (p * alpha)
-    const int chunk = (c->N + S - 1) / S;
-    hipLaunchKernelGGL(joint_mean_partial_kernel, dim3(mp / 64, S), dim3(1024), 0, c->stream, c->Wt, mp, c->N, chunk, c->zvec, mpart);
-    hipLaunchKernelGGL(joint_mean_final_kernel, dim3((m + 255) / 256), dim3(256), 0, c->stream, mpart, mp, m, nx, S, c->eval_beta,
-                       c->eval_linear ? c->eval_beta_dev : (const double*)nullptr, c->xq_dev, d, mean_dev);
+    gpg_launch_joint_mean(c, mp, m, nx, mpart, mean_dev);
     GPG_HIP_OK(c, hipMemcpyAsync(mean, mean_dev, sizeof(double) * m, hipMemcpyDeviceToHost, c->stream));
   }
   if (cov) {

@@ -19,6 +19,7 @@ from .rescaling import Rescaling, calc_dist_min, calc_dist_max
 from .hpara_optz import HparaOptz
 from .joint import draw_from_joint
 from .loo import loo_by_point, loo_by_row, point_rows
+from .second import second_from_blocks
 
 
 class DeviceChoFactor:
@@ -1371,6 +1372,45 @@ class GaussianProcess(HparaOptz):
         if rc != 0:
             raise _lib.GpgError(f'gpg_predict_joint failed ({rc}): {self._err()}')
         return mean, cov
+
+    def eval_model_second(self, x2model_in, calc_hess=True, mean_unc=False):
+        """Per-point posterior of [f, grad f] and batched Hessians at the nx query points, any nx (include/gpgrad.h:
+        gpg_predict_second; the host arithmetic is gpgradpy_amd/second.py).  Returns a SecondResult with mu, sig [nx], dmudx,
+        dsigdx [nx, dim], cov [nx, dim + 1, dim + 1] (index 0 = f(x_j), k + 1 = d f / d x_k: the point-diagonal blocks of
+        eval_model_joint(calc_grad=True), exactly symmetric and not clipped), grad_std [nx, dim] = sqrt(diag Cov(grad f)), and
+        d2mudx2, d2sigdx2 [nx, dim, dim] (None without calc_hess; d2sigdx2 is NaN where sig == 0).  mean_unc as in
+        eval_model_joint.  Gradient masks are accepted (the device honours them)."""
+        assert self.KernEta_chofac is not None, 'To evaluate the surr the Cholesky decomposition is required'
+        self._set_mean_unc(mean_unc)
+        if x2model_in.ndim == 1:
+            x2model = x2model_in[None, :]
+        elif x2model_in.ndim == 2:
+            x2model = x2model_in
+        else:
+            raise Exception(f'x2model_in should be a 2d array but it has shape {x2model_in.shape}')
+        if (self.hp_vals == self._hp_vals_model_setup) is False:
+            raise Exception('Cannot change hp_vals between calling setup_eval_model() and eval_model()')
+        if self.b_use_data_scl:
+            raise Exception('The method eval_model_second() is not setup for cases where data must be rescaled')
+        if not self._eval_ready:
+            raise Exception('setup_eval_model() must be called (again): set_data() replaced the data of the device model')
+        nx, d = x2model.shape[0], self.dim
+        xq = np.ascontiguousarray(x2model, dtype=np.float64)
+        mu, dmudx, cov = np.empty(nx), np.empty((nx, d)), np.empty((nx, d + 1, d + 1))
+        d2mudx2 = np.empty((nx, d, d)) if calc_hess else None
+        d2sigdx2 = np.empty((nx, d, d)) if calc_hess else None
+        rc = self._lib.gpg_predict_second(self._ctx, nx, _lib.as_dp(xq), float(self.hp_vals.varK), _lib.as_dp(mu), _lib.as_dp(dmudx),
+                                          _lib.as_dp(cov), None if d2mudx2 is None else _lib.as_dp(d2mudx2),
+                                          None if d2sigdx2 is None else _lib.as_dp(d2sigdx2))
+        if rc != 0:
+            raise _lib.GpgError(f'gpg_predict_second failed ({rc}): {self._err()}')
+        return second_from_blocks(mu, dmudx, cov, d2mudx2, d2sigdx2)
+
+    def set_second_chunk(self, points):
+        """Query points per chunk of eval_model_second (include/gpgrad.h: gpg_set_second_chunk; 0 = from the dimension)."""
+        rc = self._lib.gpg_set_second_chunk(self._ctx, int(points))
+        if rc != 0:
+            raise _lib.GpgError(f'gpg_set_second_chunk failed ({rc}): {self._err()}')
 
     def sample_posterior(self, x2model_in, n_samples, calc_grad=False, seed=None, z=None, mean_unc=False):
         """Draws from the joint posterior at the query points: (f_samples [n_samples, nx], g_samples [n_samples, nx, dim] or

@@ -279,6 +279,42 @@ int gpg_loo(gpg_ctx* ctx, double varK, double* resid, double* cov, double* prec,
  * products in a different order: results agree to rounding, not bitwise. */
 int gpg_set_gram_splits(gpg_ctx* ctx, int n);
 
+/* Per-point covariance of [f, grad f] and batched Hessians of the posterior at nx query points (any nx >= 1), from the factor kept
+ * by gpg_setup_eval* (the reference has no counterpart: its Hessians are one point per call and it has no gradient covariance).
+ * bs = dim + 1; index 0 is f(x_j), index k + 1 is d f / d x_k at x_j.  Every output pointer may be NULL (not all of them); what
+ * is not asked for is not computed (no sweep without gcov or a Hessian; no backward sweep and no contraction without a Hessian).
+ *   mu      [nx], dmudx [nx, dim]: posterior mean and its gradient, mean function included (beta_0 (+ xq . beta_1..d) on mu,
+ *           beta_k+1 on dmudx with mean order 1): the rows gpg_predict_joint puts in `mean`.
+ *   gcov    [nx, bs, bs] row-major: gcov_j = varK (K0 - Z_j Z_j'), Z_j the bs forward-swept cross-covariance rows of x_j and K0
+ *           the prior block of one point with itself from the kernel table (the numbers gpg_predict_joint uses): the j-th
+ *           point-diagonal block of the cov of gpg_predict_joint(with_grad = 1) without the rest of that matrix.  gcov_j[0, 0] =
+ *           sig^2, gcov_j[0, k + 1] = 1/2 d sig^2 / d x_k, gcov_j[1.., 1..] = Cov(grad f).  Exactly symmetric, not clipped.  The
+ *           training-side gradient mask is honoured, and a model built with use_grad = 0 is fine, as for gpg_predict_joint.
+ *   d2mudx2, d2sigdx2 [nx, dim, dim]: what gpg_predict_hess returns for each point, with sig and dsigdx taken from the block:
+ *           sig = sqrt(max(0, gcov_00)), dsigdx_k = gcov_0,k+1 / sig, d2sig2 = -2 varK (H2 + T), T = (Z_j Z_j')[1.., 1..],
+ *           d2sigdx2 = (d2sig2 - 2 dsigdx dsigdx') / (2 sig); NaN where sig == 0.
+ * With gpg_set_mean_uncertainty on, every block gains varK U_j H^-1 U_j' and d2sigdx2 the terms gpg_predict_hess adds; mu, dmudx
+ * and d2mudx2 do not change.
+ * The host loops over chunks of points whose rows fit the row buffer of the posterior calls: at most 4096 rows, the automatic
+ * point count the largest multiple of 64 with points * bs <= 4096 (192 points at dim 16, 448 at dim 8), and the last chunk
+ * everything that is left once its rows fit (so nx <= 4096 / bs is one chunk).  Per chunk: the cross rows
+ * and the mean as gpg_predict_joint, ONE forward sweep over all rows, a per-point Gram kernel (lane <-> query point, K-chunk
+ * partials added in chunk order by a finishing kernel, which also subtracts from K0, scales and mirrors), and for the Hessians
+ * one backward sweep of the value rows and one contraction launch with a grid over (row, point); one device-to-host copy per
+ * output and one synchronisation.  The K-chunk count is min(N_pad / 64, 64), or gpg_set_gram_splits when set: never a function of
+ * nx or of the chunk's point count.  Ordinary grids, no atomics: the same bits from run to run and under any
+ * gpg_set_max_workgroups.  -1 with a message before a successful gpg_setup_eval*, for nx < 1 and when every output is NULL.
+ * Measured on one MI355X (tools/second_time.py; n = 2000, d = 8 | n = 500, d = 4):
+ *   gcov alone at the largest nx gpg_predict_joint takes (455 | 819): 26.5 ms | 0.87 ms = forward sweep 26.1 | 0.74 ms + Gram kernel
+ *   0.122 ms (0.591 GB of Z: 4.8 TB/s) | 20.8 us (4.0 TB/s) + 0.25 | 0.11 ms for the rest, against 37.3 | 4.37 ms of gpg_predict_joint;
+ *   Hessians of 64 points in one call 8.7 | 1.05 ms against 267 | 41.5 ms for 64 gpg_predict_hess calls. */
+int gpg_predict_second(gpg_ctx* ctx, int nx, const double* xq, double varK, double* mu, double* dmudx, double* gcov,
+                       double* d2mudx2, double* d2sigdx2);
+/* Diagnostic, like gpg_set_gram_splits: query points per chunk of gpg_predict_second.  0 = automatic (above); points >= 1: that
+ * many (a multiple of 64 keeps the reads of the Gram kernel aligned), so that tests reach several chunks with a small nx.
+ * points < 0 and points (dim + 1) > 4096 return -1.  Chunked and unchunked results agree to rounding at least. */
+int gpg_set_second_chunk(gpg_ctx* ctx, int points);
+
 /* Materialisation on request (the 7-tuple of Kernel.py:307 carries N x N arrays; the fast path never
  * copies them).  out is [N, N] column-major == row-major (symmetric) for which = 0..2:
  *   0 Kern (Kernel.py:213-216), 1 Kcov (Kernel.py:237 / 277), 2 the matrix that is factorised
