@@ -1105,12 +1105,12 @@ static int predict_hess_once(gpg_ctx* c, const double* xq, double varK, double* 
   double* h1 = c->gradbuf;
   double* h2 = h1 + GPG_MAX_DIM * GPG_MAX_DIM;
   double* T = h2 + GPG_MAX_DIM * GPG_MAX_DIM;
-  gpg_launch_hess_stage(c, p, nxp, h1, h2, T, 0);
+  gpg_launch_hess_contract(c, p, 1, nxp, h1, h2);
   GPG_HIP_OK(c, hipMemsetAsync(c->Wt, 0, sizeof(double) * (size_t)nxp * c->Npad, c->stream));
-  gpg_launch_hess_stage(c, p, nxp, h1, h2, T, 1);
+  gpg_launch_hess_stage(c, p, nxp, T, 1);
   gpg_forward_rows(c, c->Wt, nxp, nxp, d + 1);
-  gpg_launch_hess_stage(c, p, nxp, h1, h2, T, 2);
-  // mean uncertainty: row 0 of Wt was t = K^-1 k + K^-1 V H^-1 u already (stage 0); the rows d_i u = e_(i+1) - W_V' z_i of the
+  gpg_launch_hess_stage(c, p, nxp, T, 2);
+  // mean uncertainty: row 0 of Wt was t = K^-1 k + K^-1 V H^-1 u already (the contraction); the rows d_i u = e_(i+1) - W_V' z_i of the
   // swept derivative rows 1 .. d give the last term, 2 d_i u' H^-1 d_k u = 2 c'_i . c'_k
   const bool munc = c->mean_unc != 0;
   const int nb = c->n_beta;

@@ -14,6 +14,7 @@
 // the (d+1)(d+2)/2 block entries of the ordered pair (a, b) that fall in the lower triangle.
 #include <cstring>
 #include "gpg_internal.h"
+#include "kernel_fn.h"
 
 namespace {
 
@@ -142,36 +143,15 @@ __global__ void __launch_bounds__(256) assemble_kernel(AsmParams P, const double
   const int mode = P.mode, precon = P.precon, ld = P.ld;
   const double varK = P.varK, eta = P.eta;
   const int bend = min(tb, n - b0);
-  const double sqrt5 = sqrt(5.0);
-  const double rq_alpha = P.hp_kernel, rq_const = 4.0 * (1.0 + 1.0 / P.hp_kernel);   // KernelRatQuad.py:529
+  const double rq_c = kern_rq_c(P.hp_kernel);
 
   for (int bb = 0; bb < bend; ++bb) {
     const int b = b0 + bb;
-    double R[D];
-    double E, M1 = 0.0, K00;
-    if (KERN == GPG_KERNEL_SQEXP) {
-      double s = 0.0;
+    double R[D], s = 0.0;
 #pragma unroll
-      for (int k = 0; k < D; ++k) { R[k] = xa[k] - xb[bb][k]; s -= th[k] * (R[k] * R[k]); }
-      E = exp(s);
-      K00 = E;
-    } else if (KERN == GPG_KERNEL_RATQU) {   // KernelRatQuad.py:463-476: B = 1 + sum theta R^2 / alpha
-      double s = 0.0;
-#pragma unroll
-      for (int k = 0; k < D; ++k) { R[k] = xa[k] - xb[bb][k]; s += th[k] * (R[k] * R[k]); }
-      const double Bq = 1.0 + s / rq_alpha;
-      K00 = pow(Bq, -rq_alpha);
-      M1 = pow(Bq, -rq_alpha - 1.0);
-      E = pow(Bq, -rq_alpha - 2.0);            // B^(-alpha-2) takes the place of E in the second derivatives
-    } else {
-      double s = 0.0;
-#pragma unroll
-      for (int k = 0; k < D; ++k) { R[k] = xa[k] - xb[bb][k]; s += th[k] * (R[k] * R[k]); }
-      double nu = sqrt(s);
-      E = exp(-sqrt5 * nu);                       // Abase
-      M1 = ((5.0 / 3.0) * (1.0 + sqrt5 * nu)) * E;  // mat1
-      K00 = (1.0 + sqrt5 * nu + (5.0 / 3.0) * (nu * nu)) * E;
-    }
+    for (int k = 0; k < D; ++k) { R[k] = xa[k] - xb[bb][k]; kern_s_add<KERN, true>(s, th[k], R[k]); }
+    const KernRadial rad = kern_radial<KERN, true>(s, P.hp_kernel);
+    const double E = rad.E, M1 = rad.M1, K00 = rad.K00;
     const bool diag_pt = (a == b);
     const bool low_pt = (a >= b);
     const int gpbb = gpb[bb];
@@ -208,29 +188,12 @@ __global__ void __launch_bounds__(256) assemble_kernel(AsmParams P, const double
     if (nblk > 1) {
 #pragma unroll
       for (int i = 0; i < D; ++i) {
-        double vi0, vii;
-        if (KERN == GPG_KERNEL_SQEXP) {
-          vi0 = ((-2.0 * th[i]) * R[i]) * E;
-          vii = (2.0 * th[i] - (4.0 * (th[i] * th[i])) * (R[i] * R[i])) * E;
-        } else if (KERN == GPG_KERNEL_RATQU) {   // KernelRatQuad.py:539-544
-          vi0 = ((-2.0 * th[i]) * R[i]) * M1;
-          vii = (2.0 * th[i]) * M1 - ((rq_const * (th[i] * th[i])) * (R[i] * R[i])) * E;
-        } else {
-          vi0 = ((-th[i]) * R[i]) * M1;
-          vii = th[i] * M1 - (((25.0 / 3.0) * (th[i] * th[i])) * (R[i] * R[i])) * E;
-        }
-        emit(i + 1, 0, vi0);
-        if (low_pt) emit(i + 1, i + 1, vii);
+        emit(i + 1, 0, kern_d10<KERN>(th[i], R[i], E, M1));
+        if (low_pt) emit(i + 1, i + 1, kern_d11_diag<KERN>(th[i], R[i], E, M1, rq_c));
 #pragma unroll
-        for (int j = 0; j < D; ++j) {
-          if (j < i) {  // block row i+1 > block column j+1; the reference's (lo, hi) = (j, i) ordering
-            double vij;
-            if (KERN == GPG_KERNEL_SQEXP) vij = ((-4.0 * th[j]) * th[i]) * ((R[j] * R[i]) * E);
-            else if (KERN == GPG_KERNEL_RATQU) vij = (((((-rq_const) * th[j]) * th[i]) * R[j]) * R[i]) * E;   // :554
-            else vij = (((((-(25.0 / 3.0)) * th[j]) * th[i]) * R[j]) * R[i]) * E;
-            emit(i + 1, j + 1, vij);
-          }
-        }
+        for (int j = 0; j < D; ++j)
+          if (j < i)   // block row i+1 > block column j+1; the reference's (lo, hi) = (j, i) ordering
+            emit(i + 1, j + 1, kern_d11_off<KERN>(th[j], th[i], R[j], R[i], E, rq_c));
       }
     }
   }
@@ -248,33 +211,13 @@ __global__ void __launch_bounds__(256) cross_kernel(AsmParams P, const double* _
   if (a_ll >= P.n) return;
   const int a = (int)a_ll, n = P.n;
   const int nblk = P.use_grad ? D + 1 : 1;
-  double R[D];
-  double E, M1 = 0.0, K00;
-  const double sqrt5 = sqrt(5.0);
+  double R[D], E, M1 = 0.0, K00;
   if (j < nx) {
-    if (KERN == GPG_KERNEL_SQEXP) {
-      double s = 0.0;
+    double s = 0.0;
 #pragma unroll
-      for (int k = 0; k < D; ++k) { R[k] = Xt[(size_t)k * n + a] - Xq[(size_t)k * nxp + j]; s -= P.theta[k] * (R[k] * R[k]); }
-      E = exp(s);
-      K00 = E;
-    } else if (KERN == GPG_KERNEL_RATQU) {
-      double s = 0.0;
-#pragma unroll
-      for (int k = 0; k < D; ++k) { R[k] = Xt[(size_t)k * n + a] - Xq[(size_t)k * nxp + j]; s += P.theta[k] * (R[k] * R[k]); }
-      const double Bq = 1.0 + s / P.hp_kernel;
-      K00 = pow(Bq, -P.hp_kernel);
-      M1 = pow(Bq, -P.hp_kernel - 1.0);
-      E = 0.0;
-    } else {
-      double s = 0.0;
-#pragma unroll
-      for (int k = 0; k < D; ++k) { R[k] = Xt[(size_t)k * n + a] - Xq[(size_t)k * nxp + j]; s += P.theta[k] * (R[k] * R[k]); }
-      double nu = sqrt(s);
-      E = exp(-sqrt5 * nu);
-      M1 = ((5.0 / 3.0) * (1.0 + sqrt5 * nu)) * E;
-      K00 = (1.0 + sqrt5 * nu + (5.0 / 3.0) * (nu * nu)) * E;
-    }
+    for (int k = 0; k < D; ++k) { R[k] = Xt[(size_t)k * n + a] - Xq[(size_t)k * nxp + j]; kern_s_add<KERN, true>(s, P.theta[k], R[k]); }
+    const KernRadial rad = kern_radial<KERN, true>(s, P.hp_kernel);
+    E = rad.E; M1 = rad.M1; K00 = rad.K00;
   }
   const int gpa = P.gpos[a];
   for (int I = 0; I < nblk; ++I) {
@@ -282,10 +225,7 @@ __global__ void __launch_bounds__(256) cross_kernel(AsmParams P, const double* _
     const size_t c = I == 0 ? (size_t)a : (size_t)n + (size_t)(I - 1) * P.ng + gpa;
     double v = 0.0;
     if (j < nx) {
-      if (I == 0) v = K00;
-      else if (KERN == GPG_KERNEL_SQEXP) v = ((-2.0 * P.theta[I - 1]) * R[I - 1]) * E;
-      else if (KERN == GPG_KERNEL_RATQU) v = ((-2.0 * P.theta[I - 1]) * R[I - 1]) * M1;   // KernelRatQuad.py:540
-      else v = ((-P.theta[I - 1]) * R[I - 1]) * M1;
+      v = I == 0 ? K00 : kern_d10<KERN>(P.theta[I - 1], R[I - 1], E, M1);
       v *= invp[c];
     }
     Wt[c * nxp + j] = v;
@@ -309,55 +249,24 @@ __global__ void __launch_bounds__(256) rtensor_kern_kernel(RtParams P, const dou
   const int d = P.d;
   double R[GPG_MAX_DIM];
   double s = 0.0;
-  for (int k = 0; k < d; ++k) {
-    R[k] = Rt[(size_t)k * np + t];
-    if (KERN == GPG_KERNEL_SQEXP) s -= P.theta[k] * (R[k] * R[k]);
-    else s += P.theta[k] * (R[k] * R[k]);
-  }
-  double E, M1 = 0.0, K00, c2;                      // c2: factor of the mixed second derivatives
-  if (KERN == GPG_KERNEL_SQEXP) {
-    E = exp(s); K00 = E; c2 = -4.0;
-  } else if (KERN == GPG_KERNEL_RATQU) {
-    const double Bq = 1.0 + s / P.hp_kernel;
-    K00 = pow(Bq, -P.hp_kernel);
-    M1 = pow(Bq, -P.hp_kernel - 1.0);
-    E = pow(Bq, -P.hp_kernel - 2.0);
-    c2 = -(4.0 * (1.0 + 1.0 / P.hp_kernel));
-  } else {
-    const double sqrt5 = sqrt(5.0), nu = sqrt(s);
-    E = exp(-sqrt5 * nu);
-    M1 = ((5.0 / 3.0) * (1.0 + sqrt5 * nu)) * E;
-    K00 = (1.0 + sqrt5 * nu + (5.0 / 3.0) * (nu * nu)) * E;
-    c2 = -(25.0 / 3.0);
-  }
+  for (int k = 0; k < d; ++k) { R[k] = Rt[(size_t)k * np + t]; kern_s_add<KERN, true>(s, P.theta[k], R[k]); }
+  const KernRadial rad = kern_radial<KERN, true>(s, P.hp_kernel);
+  const double E = rad.E, M1 = rad.M1, K00 = rad.K00, rq_c = kern_rq_c(P.hp_kernel);
   const size_t C2 = (size_t)P.n2 + (P.use_grad ? (size_t)P.n2g * d : 0);
   out[(size_t)a * C2 + b] = K00;
   if (!P.use_grad) return;
   const int g1 = gpos1[a], g2 = gpos2[b];
   for (int i = 0; i < d; ++i) {
     const double th = P.theta[i];
-    double v10, v01, vii;
-    if (KERN == GPG_KERNEL_SQEXP) {
-      v10 = ((-2.0 * th) * R[i]) * E;
-      v01 = ((2.0 * th) * R[i]) * E;
-      vii = (2.0 * th - (4.0 * (th * th)) * (R[i] * R[i])) * E;
-    } else if (KERN == GPG_KERNEL_RATQU) {
-      v10 = ((-2.0 * th) * R[i]) * M1;
-      v01 = ((2.0 * th) * R[i]) * M1;
-      vii = (2.0 * th) * M1 - (((-c2) * (th * th)) * (R[i] * R[i])) * E;
-    } else {
-      v10 = ((-th) * R[i]) * M1;
-      v01 = (th * R[i]) * M1;
-      vii = th * M1 - (((25.0 / 3.0) * (th * th)) * (R[i] * R[i])) * E;
-    }
+    const double v10 = kern_d10<KERN>(th, R[i], E, M1), v01 = kern_d01<KERN>(th, R[i], E, M1);
+    const double vii = kern_d11_diag<KERN>(th, R[i], E, M1, rq_c);
     const size_t ri = (size_t)P.n1 + (size_t)i * P.n1g + g1, ci = (size_t)P.n2 + (size_t)i * P.n2g + g2;
     if (g1 >= 0) out[ri * C2 + b] = v10;
     if (g2 >= 0) out[(size_t)a * C2 + ci] = v01;
     if (g1 >= 0 && g2 >= 0) {
       out[ri * C2 + ci] = vii;
       for (int j = i + 1; j < d; ++j) {
-        const double term = KERN == GPG_KERNEL_SQEXP ? ((-4.0 * th) * P.theta[j]) * ((R[i] * R[j]) * E)
-                                                     : (((c2 * th) * P.theta[j]) * R[i]) * R[j] * E;
+        const double term = kern_d11_off<KERN>(th, P.theta[j], R[i], R[j], E, rq_c);   // (lo, hi) = (i, j)
         const size_t rj = (size_t)P.n1 + (size_t)j * P.n1g + g1, cj = (size_t)P.n2 + (size_t)j * P.n2g + g2;
         out[ri * C2 + cj] = term;
         out[rj * C2 + ci] = term;
@@ -366,40 +275,17 @@ __global__ void __launch_bounds__(256) rtensor_kern_kernel(RtParams P, const dou
   }
 }
 
-template <int KERN>
-void launch_assemble_d(gpg_ctx* c, const AsmParams& p, int B, const gpg_batch_item* items, size_t v_stride, size_t a_stride) {
+void launch_assemble(gpg_ctx* c, const AsmParams& p, int B, const gpg_batch_item* items, size_t v_stride, size_t a_stride) {
   // every thread owns one point a and walks the tb points b of its workgroup one after the other (~2.5 us per pair at d = 4): small
   // data sets get fewer points b per workgroup, so that the launch is ~1000 workgroups wide instead of n / 16 deep chains
   const long wide = (long)((p.n + 255) / 256) * p.n * B;
   int tb = wide >= 8192 ? kTB : (int)(wide / 1024);
   tb = tb < 1 ? 1 : (tb > kTB ? kTB : tb);
   dim3 grid((p.n + 255) / 256, (p.n + tb - 1) / tb, B);
-#define CASE_D(DD)                                                                                  \
-  case DD:                                                                                          \
-    hipLaunchKernelGGL((assemble_kernel<KERN, DD>), grid, dim3(256), 0, c->stream, p, c->Xt, c->dvec, \
-                       c->invp, c->A, items, v_stride, a_stride, tb);                               \
-    break;
-  switch (p.d) {
-    CASE_D(1) CASE_D(2) CASE_D(3) CASE_D(4) CASE_D(5) CASE_D(6) CASE_D(7) CASE_D(8)
-    CASE_D(9) CASE_D(10) CASE_D(11) CASE_D(12) CASE_D(13) CASE_D(14) CASE_D(15) CASE_D(16)
-  }
-#undef CASE_D
-}
-
-template <int KERN>
-void launch_cross_d(gpg_ctx* c, const AsmParams& p, int nx, int nxp) {
-  long long total = (long long)p.n * nxp;
-  dim3 grid((unsigned)((total + 255) / 256));
-#define CASE_D(DD)                                                                                   \
-  case DD:                                                                                           \
-    hipLaunchKernelGGL((cross_kernel<KERN, DD>), grid, dim3(256), 0, c->stream, p, c->Xt, c->xq_dev, nx, \
-                       nxp, c->invp, c->Wt);                                                         \
-    break;
-  switch (p.d) {
-    CASE_D(1) CASE_D(2) CASE_D(3) CASE_D(4) CASE_D(5) CASE_D(6) CASE_D(7) CASE_D(8)
-    CASE_D(9) CASE_D(10) CASE_D(11) CASE_D(12) CASE_D(13) CASE_D(14) CASE_D(15) CASE_D(16)
-  }
-#undef CASE_D
+  gpg_for_kern_d(p.kernel, p.d, [&](auto K, auto D) {
+    hipLaunchKernelGGL((assemble_kernel<decltype(K)::value, decltype(D)::value>), grid, dim3(256), 0, c->stream, p, c->Xt, c->dvec,
+                       c->invp, c->A, items, v_stride, a_stride, tb);
+  });
 }
 
 }  // namespace
@@ -419,9 +305,7 @@ void gpg_launch_prep(gpg_ctx* c, const AsmParams& p, double var_fval, double var
 void gpg_launch_assembly(gpg_ctx* c, const AsmParams& p) {
   double bytes = 8.0 * (double)p.N * ((double)p.N + 1.0) / 2.0;
   gpg_prof_begin(c, GPG_PROF_ASSEMBLY, bytes);
-  if (p.kernel == GPG_KERNEL_SQEXP) launch_assemble_d<GPG_KERNEL_SQEXP>(c, p, 1, nullptr, 0, 0);
-  else if (p.kernel == GPG_KERNEL_RATQU) launch_assemble_d<GPG_KERNEL_RATQU>(c, p, 1, nullptr, 0, 0);
-  else launch_assemble_d<GPG_KERNEL_MA5F2>(c, p, 1, nullptr, 0, 0);
+  launch_assemble(c, p, 1, nullptr, 0, 0);
   gpg_prof_end(c);
 }
 
@@ -437,9 +321,7 @@ void gpg_launch_prep_assembly_batch(gpg_ctx* c, const AsmParams& p, int B, const
                      items, v_stride, a_stride, c->n_beta, c->Xt, (const double*)nullptr);
   double bytes = 8.0 * (double)p.N * ((double)p.N + 1.0) / 2.0 * B;
   gpg_prof_begin(c, GPG_PROF_ASSEMBLY, bytes);
-  if (p.kernel == GPG_KERNEL_SQEXP) launch_assemble_d<GPG_KERNEL_SQEXP>(c, p, B, items, v_stride, a_stride);
-  else if (p.kernel == GPG_KERNEL_RATQU) launch_assemble_d<GPG_KERNEL_RATQU>(c, p, B, items, v_stride, a_stride);
-  else launch_assemble_d<GPG_KERNEL_MA5F2>(c, p, B, items, v_stride, a_stride);
+  launch_assemble(c, p, B, items, v_stride, a_stride);
   gpg_prof_end(c);
 }
 
@@ -466,9 +348,12 @@ void gpg_launch_abs_rowsum(gpg_ctx* c, double scale, double* out_dev) {
 }
 
 void gpg_launch_cross(gpg_ctx* c, const AsmParams& p, int nx, int nxp) {
-  if (p.kernel == GPG_KERNEL_SQEXP) launch_cross_d<GPG_KERNEL_SQEXP>(c, p, nx, nxp);
-  else if (p.kernel == GPG_KERNEL_RATQU) launch_cross_d<GPG_KERNEL_RATQU>(c, p, nx, nxp);
-  else launch_cross_d<GPG_KERNEL_MA5F2>(c, p, nx, nxp);
+  const long long total = (long long)p.n * nxp;
+  const dim3 grid((unsigned)((total + 255) / 256));
+  gpg_for_kern_d(p.kernel, p.d, [&](auto K, auto D) {
+    hipLaunchKernelGGL((cross_kernel<decltype(K)::value, decltype(D)::value>), grid, dim3(256), 0, c->stream, p, c->Xt, c->xq_dev, nx,
+                       nxp, c->invp, c->Wt);
+  });
 }
 
 // d K / d theta_k (and d K / d alpha for the rational quadratic kernel) of the kernel matrix of ONE point set with itself, from
@@ -493,21 +378,13 @@ __global__ void __launch_bounds__(256) rtensor_kern_dhp_kernel(RtParams P, const
   for (int k = 0; k < d; ++k) { R[k] = Rt[(size_t)k * np + t]; th[k] = P.theta[k]; s += th[k] * (R[k] * R[k]); }
   const double sqrt5 = sqrt(5.0), al = P.hp_kernel;
   // f0 = value, f1 / f2 / f3: the factors the first / second / third derivative levels multiply (E, M1, ... of gradient.hip)
-  double f0, f1 = 0.0, f2, f3 = 0.0, inu = 0.0, G0 = 0.0, G1 = 0.0, G2 = 0.0;
+  const KernRadial rad = kern_radial<KERN>(s, al);
+  const double f0 = rad.K00, f1 = rad.M1, f2 = rad.E, f3 = rad.F3, inu = rad.inu;
+  double G0 = 0.0, G1 = 0.0, G2 = 0.0;
   const double s1 = 1.0 + 1.0 / al, s2 = s1 * (1.0 + 2.0 / al), cq = 4.0 * s1, dcq = 4.0 / (al * al);
-  if (KERN == GPG_KERNEL_SQEXP) {
-    f2 = exp(-s); f0 = f2;
-  } else if (KERN == GPG_KERNEL_RATQU) {
-    const double Bq = 1.0 + s / al;
-    f0 = pow(Bq, -al); f1 = pow(Bq, -al - 1.0); f2 = pow(Bq, -al - 2.0); f3 = pow(Bq, -al - 3.0);
-    const double lnB = log(Bq), om = 1.0 - 1.0 / Bq;
+  if (KERN == GPG_KERNEL_RATQU) {
+    const double lnB = log(rad.Bq), om = 1.0 - 1.0 / rad.Bq;
     G0 = -lnB + om; G1 = -lnB + s1 * om; G2 = -lnB + (1.0 + 2.0 / al) * om;
-  } else {
-    const double nu = sqrt(s);
-    f2 = exp(-sqrt5 * nu);
-    f1 = ((5.0 / 3.0) * (1.0 + sqrt5 * nu)) * f2;
-    f0 = (1.0 + sqrt5 * nu + (5.0 / 3.0) * (nu * nu)) * f2;
-    inu = 1.0 / fmax(nu, 1e-16);
   }
   auto put = [&](size_t r, size_t c, int k, double v) { out_th[(size_t)k * NN + r * N + c] = v; };
   // ---- block (0, 0)
@@ -520,7 +397,7 @@ __global__ void __launch_bounds__(256) rtensor_kern_dhp_kernel(RtParams P, const
   for (int i = 0; i < d; ++i) {
     const size_t ri = (size_t)(i + 1) * n + a, ci = (size_t)(i + 1) * n + b;
     // ---- blocks (i+1, 0) and (0, i+1)
-    const double v = KERN == GPG_KERNEL_SQEXP ? ((-2.0 * th[i]) * R[i]) * f2 : KERN == GPG_KERNEL_RATQU ? ((-2.0 * th[i]) * R[i]) * f1 : ((-th[i]) * R[i]) * f1;
+    const double v = kern_d10<KERN>(th[i], R[i], f2, f1);
     if (out_th)
       for (int k = 0; k < d; ++k) {
         const double rk2 = R[k] * R[k];
@@ -591,20 +468,14 @@ __global__ void __launch_bounds__(256) rtensor_kern_hess_x_kernel(RtParams P, co
   double tR[GPG_MAX_DIM], th[GPG_MAX_DIM];
   double s = 0.0;
   for (int k = 0; k < d; ++k) { const double r = Rt[(size_t)k * np + t]; th[k] = P.theta[k]; tR[k] = th[k] * r; s += tR[k] * r; }
-  const double sqrt5 = sqrt(5.0), al = P.hp_kernel, s1 = 1.0 + 1.0 / al, s2 = s1 * (1.0 + 2.0 / al);
-  double E, M1 = 0.0, F3 = 0.0, c3 = 0.0;
-  if (KERN == GPG_KERNEL_SQEXP) E = exp(-s);
-  else if (KERN == GPG_KERNEL_RATQU) { const double Bq = 1.0 + s / al; M1 = pow(Bq, -al - 1.0); E = pow(Bq, -al - 2.0); F3 = pow(Bq, -al - 3.0); }
-  else { const double nu = sqrt(s); E = exp(-sqrt5 * nu); M1 = ((5.0 / 3.0) * (1.0 + sqrt5 * nu)) * E; c3 = sqrt5 / fmax(nu, 1e-16); }
+  const double al = P.hp_kernel, s1 = 1.0 + 1.0 / al, s2 = s1 * (1.0 + 2.0 / al);
+  const KernRadial rad = kern_radial<KERN>(s, al);
+  const double E = rad.E, M1 = rad.M1, F3 = rad.F3, c3 = rad.c3;
   const int gb = P.use_grad ? gpos2[b] : -1;
   for (int k = 0; k < d; ++k)
     for (int i = 0; i < d; ++i) {
       double* row = out + ((size_t)k * Rw + (size_t)i * n1 + a) * C;
-      double v;
-      if (KERN == GPG_KERNEL_SQEXP) v = (4.0 * tR[i] * tR[k] - (i == k ? 2.0 * th[i] : 0.0)) * E;
-      else if (KERN == GPG_KERNEL_RATQU) v = (4.0 * s1) * tR[i] * tR[k] * E - (i == k ? 2.0 * th[i] * M1 : 0.0);
-      else v = (25.0 / 3.0) * tR[i] * tR[k] * E - (i == k ? th[k] * M1 : 0.0);
-      row[b] = v;
+      row[b] = kern_d2k_base<KERN>(i, k, th[i], th[k], tR[i], tR[k], E, M1, s1);
       if (gb < 0) continue;
       for (int j = 0; j < d; ++j) {
         const double lin = (i == k ? th[i] * tR[j] : 0.0) + (j == k ? th[j] * tR[i] : 0.0) + (i == j ? th[i] * tR[k] : 0.0);

@@ -15,18 +15,14 @@
 // Output per hyperparameter slot k in [0, d+3): theta_0..theta_(d-1), varK, var_fval, var_fgrad:
 //   g_aa[k] = sum G_k o (alpha alpha^T),  g_inv[k] = sum G_k o (-1/2 Kcov^-1);  the host combines s*g_aa + g_inv.
 #include "gpg_internal.h"
+#include "device_util.h"
+#include "kernel_fn.h"
 
 namespace {
 
 constexpr int kTBg = 16;          // b-points staged per workgroup (at most)
 // Small designs: fewer b-points per workgroup, so that the launch has enough workgroups for the chip (n = 500: 64 -> 250).
 static inline int grad_tb(int n) { return n <= 256 ? 1 : n <= 1024 ? 4 : kTBg; }
-
-__device__ __forceinline__ double wave_sum_g(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
 
 // RHS row 0 <- RHS row 1 - beta * RHS row 0  ( = L^-1 P^-1 (y - V beta) ), beta from the reduction scalars;
 // first-order mean (nb = d + 1 > 1): RHS row 0 <- w_y - sum_i beta_i w_i with w_i = RHS row i, w_y = RHS row nb, beta from betav
@@ -122,7 +118,7 @@ __global__ void __launch_bounds__(256, 2) grad_contract_kernel(AsmParams P, cons
     const int precon = P.precon;
     const int bend = min(tb, n - b0);
     const double sqrt5 = sqrt(5.0);
-    const double rq_alpha = P.hp_kernel, rq_s1 = 1.0 + 1.0 / P.hp_kernel, rq_s2 = rq_s1 * (1.0 + 2.0 / P.hp_kernel);   // scalar1, scalar2 (:704-705)
+    const double rq_s1 = 1.0 + 1.0 / P.hp_kernel, rq_s2 = rq_s1 * (1.0 + 2.0 / P.hp_kernel);   // scalar1, scalar2 (:704-705)
     const double rq_c = 4.0 * rq_s1, rq_dc = 4.0 / (P.hp_kernel * P.hp_kernel);          // const (:529) and -d const / d alpha
 
     for (int bb = 0; bb < bend; ++bb) {
@@ -130,38 +126,19 @@ __global__ void __launch_bounds__(256, 2) grad_contract_kernel(AsmParams P, cons
       if (b > a) continue;                                   // lower triangle of point pairs only ...
       const bool diag_pt = (a == b);
       const int gpbb = gpb[bb];
-      double R[D], E, M1 = 0.0, inu = 0.0, K00, F3 = 0.0, G0 = 0.0, G1 = 0.0, G2 = 0.0;
-      if (KERN == GPG_KERNEL_SQEXP) {
-        double s = 0.0;
+      double R[D], s = 0.0, G0 = 0.0, G1 = 0.0, G2 = 0.0;
 #pragma unroll
-        for (int k = 0; k < D; ++k) { R[k] = xa[k] - xb[bb][k]; s -= th[k] * (R[k] * R[k]); }
-        E = exp(s);
-        K00 = E;
-      } else if (KERN == GPG_KERNEL_RATQU) {
-        // KernelRatQuad.py:656-667, 770-790: f_p = B^(-alpha-p), B = 1 + sum theta R^2 / alpha;
+      for (int k = 0; k < D; ++k) { R[k] = xa[k] - xb[bb][k]; kern_s_add<KERN, true>(s, th[k], R[k]); }
+      const KernRadial rad = kern_radial<KERN, true>(s, P.hp_kernel);
+      const double E = rad.E, M1 = rad.M1, K00 = rad.K00, F3 = rad.F3, inu = rad.inu;
+      if (KERN == GPG_KERNEL_RATQU) {
+        // KernelRatQuad.py:656-667, 770-790: f_p = B^(-alpha-p), B = 1 + sum theta R^2 / alpha (K00, M1, E, F3 = f_0 .. f_3);
         //   d f_p / d theta_k = -(1 + p/alpha) R_k^2 f_(p+1),   d f_p / d alpha = f_p g_p,
         //   g_p = -ln B + (1 + p/alpha) (1 - 1/B)
-        double s = 0.0;
-#pragma unroll
-        for (int k = 0; k < D; ++k) { R[k] = xa[k] - xb[bb][k]; s += th[k] * (R[k] * R[k]); }
-        const double Bq = 1.0 + s / rq_alpha;
-        K00 = pow(Bq, -rq_alpha);
-        M1 = pow(Bq, -rq_alpha - 1.0);          // f_1
-        E = pow(Bq, -rq_alpha - 2.0);           // f_2
-        F3 = pow(Bq, -rq_alpha - 3.0);          // f_3
-        const double lnB = log(Bq), om = 1.0 - 1.0 / Bq;
+        const double lnB = log(rad.Bq), om = 1.0 - 1.0 / rad.Bq;
         G0 = -lnB + om;
-        G1 = -lnB + (1.0 + 1.0 / rq_alpha) * om;
-        G2 = -lnB + (1.0 + 2.0 / rq_alpha) * om;
-      } else {
-        double s = 0.0;
-#pragma unroll
-        for (int k = 0; k < D; ++k) { R[k] = xa[k] - xb[bb][k]; s += th[k] * (R[k] * R[k]); }
-        const double nu = sqrt(s);
-        E = exp(-sqrt5 * nu);
-        M1 = ((5.0 / 3.0) * (1.0 + sqrt5 * nu)) * E;
-        K00 = (1.0 + sqrt5 * nu + (5.0 / 3.0) * (nu * nu)) * E;
-        inu = 1.0 / fmax(nu, 1e-16);                         // KernelMatern5f2.py:592
+        G1 = -lnB + (1.0 + 1.0 / P.hp_kernel) * om;
+        G2 = -lnB + (1.0 + 2.0 / P.hp_kernel) * om;
       }
       // one matrix entry (I, J) at the point pair (a, b): value v, d v / d theta_k in dv[k]
       auto contract = [&](int I, int J, double v, const double (&dv)[D], double wgt, double da = 0.0) {
@@ -205,19 +182,21 @@ __global__ void __launch_bounds__(256, 2) grad_contract_kernel(AsmParams P, cons
 #pragma unroll
         for (int i = 0; i < D; ++i) {
           // ---- block (i+1, 0) at (a, b)  and, for a != b, block (i+1, 0) at (b, a) = -value (R -> -R)
+          // (v here, and w below, are assigned inside each branch: hoisted in front of it, the same call changes the generated code
+          // of 36 of the 48 instantiations, tools/isa_diff.py)
           double v, dav = 0.0;
           if (KERN == GPG_KERNEL_SQEXP) {
-            v = ((-2.0 * th[i]) * R[i]) * E;
+            v = kern_d10<KERN>(th[i], R[i], E, M1);
 #pragma unroll
             for (int k = 0; k < D; ++k) dv[k] = -(R[k] * R[k]) * v + (k == i ? -2.0 * R[i] * E : 0.0);
           } else if (KERN == GPG_KERNEL_RATQU) {
-            v = ((-2.0 * th[i]) * R[i]) * M1;
+            v = kern_d10<KERN>(th[i], R[i], E, M1);
 #pragma unroll
             for (int k = 0; k < D; ++k)
               dv[k] = (2.0 * rq_s1) * th[i] * R[i] * (R[k] * R[k]) * E + (k == i ? -2.0 * R[i] * M1 : 0.0);   // :712-722
             dav = v * G1;
           } else {
-            v = ((-th[i]) * R[i]) * M1;
+            v = kern_d10<KERN>(th[i], R[i], E, M1);
 #pragma unroll
             for (int k = 0; k < D; ++k)
               dv[k] = (25.0 / 6.0) * th[i] * R[i] * (R[k] * R[k]) * E + (k == i ? -R[i] * M1 : 0.0);
@@ -253,7 +232,7 @@ __global__ void __launch_bounds__(256, 2) grad_contract_kernel(AsmParams P, cons
               double w, daw = 0.0;
               if (KERN == GPG_KERNEL_RATQU) {
                 if (i == j) {                                             // KernelRatQuad.py:544 / :709,729-736 / :820-830
-                  w = (2.0 * th[i]) * M1 - ((rq_c * (th[i] * th[i])) * (R[i] * R[i])) * E;
+                  w = kern_d11_diag<KERN>(th[i], R[i], E, M1, rq_c);
 #pragma unroll
                   for (int k = 0; k < D; ++k)
                     dv[k] = -(2.0 * rq_s1) * th[i] * (R[k] * R[k]) * E +
@@ -261,7 +240,7 @@ __global__ void __launch_bounds__(256, 2) grad_contract_kernel(AsmParams P, cons
                             (k == i ? 2.0 * M1 - (8.0 * rq_s1) * th[i] * (R[i] * R[i]) * E : 0.0);
                   daw = (2.0 * th[i]) * M1 * G1 + (rq_dc - rq_c * G2) * (th[i] * th[i]) * (R[i] * R[i]) * E;
                 } else {                                                  // :554 / :724-727,738-743
-                  w = (((((-rq_c) * th[j]) * th[i]) * R[j]) * R[i]) * E;
+                  w = kern_d11_off<KERN>(th[j], th[i], R[j], R[i], E, rq_c);
 #pragma unroll
                   for (int k = 0; k < D; ++k)
                     dv[k] = (4.0 * rq_s2) * th[i] * th[j] * (R[i] * R[j]) * (R[k] * R[k]) * F3 +
@@ -271,12 +250,12 @@ __global__ void __launch_bounds__(256, 2) grad_contract_kernel(AsmParams P, cons
                 }
               } else if (KERN == GPG_KERNEL_SQEXP) {
                 if (i == j) {
-                  w = (2.0 * th[i] - (4.0 * (th[i] * th[i])) * (R[i] * R[i])) * E;
+                  w = kern_d11_diag<KERN>(th[i], R[i], E, M1, rq_c);
 #pragma unroll
                   for (int k = 0; k < D; ++k)
                     dv[k] = -(R[k] * R[k]) * w + (k == i ? (2.0 - 8.0 * th[i] * (R[i] * R[i])) * E : 0.0);
                 } else {
-                  w = ((-4.0 * th[j]) * th[i]) * ((R[j] * R[i]) * E);
+                  w = kern_d11_off<KERN>(th[j], th[i], R[j], R[i], E, rq_c);
 #pragma unroll
                   for (int k = 0; k < D; ++k)
                     dv[k] = -(R[k] * R[k]) * w + (k == i ? -4.0 * th[j] * (R[i] * R[j]) * E : 0.0) +
@@ -284,14 +263,14 @@ __global__ void __launch_bounds__(256, 2) grad_contract_kernel(AsmParams P, cons
                 }
               } else {
                 if (i == j) {
-                  w = th[i] * M1 - (((25.0 / 3.0) * (th[i] * th[i])) * (R[i] * R[i])) * E;
+                  w = kern_d11_diag<KERN>(th[i], R[i], E, M1, rq_c);
 #pragma unroll
                   for (int k = 0; k < D; ++k)
                     dv[k] = -((25.0 / 6.0) * th[i]) * (R[k] * R[k]) * E +
                             ((25.0 * sqrt5 / 6.0) * (th[i] * th[i])) * (R[i] * R[i]) * (R[k] * R[k]) * inu * E +
                             (k == i ? M1 - ((50.0 / 3.0) * th[i]) * (R[i] * R[i]) * E : 0.0);
                 } else {
-                  w = (((((-(25.0 / 3.0)) * th[j]) * th[i]) * R[j]) * R[i]) * E;
+                  w = kern_d11_off<KERN>(th[j], th[i], R[j], R[i], E, rq_c);
 #pragma unroll
                   for (int k = 0; k < D; ++k)
                     dv[k] = ((25.0 * sqrt5 / 6.0) * th[i] * th[j]) * (R[i] * R[j]) * (R[k] * R[k]) * inu * E +
@@ -334,7 +313,7 @@ __global__ void __launch_bounds__(256, 2) grad_contract_kernel(AsmParams P, cons
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
   for (int k = 0; k < NS; ++k) {
-    const double s1 = wave_sum_g(ga[k]), s2 = wave_sum_g(gi[k]);
+    const double s1 = wave_sum(ga[k]), s2 = wave_sum(gi[k]);
     if (lane == 0) { red[k][w] = s1; red[NS + k][w] = s2; }
   }
   __syncthreads();
@@ -351,22 +330,8 @@ __global__ void grad_final_reduce_kernel(const double* __restrict__ partial, int
   if (k >= nvals) return;
   double s = 0.0;
   for (int b = lane; b < nblocks; b += 64) s += partial[(size_t)b * (2 * GPG_GRAD_SLOTS_MAX) + k];
-  s = wave_sum_g(s);
+  s = wave_sum(s);
   if (lane == 0) out[k] = s;
-}
-
-template <int KERN>
-void launch_contract_d(gpg_ctx* c, const AsmParams& p, double* partial, dim3 grid, const double* zvec, const double* Minv, int tb) {
-#define CASE_D(DD)                                                                                               \
-  case DD:                                                                                                       \
-    hipLaunchKernelGGL((grad_contract_kernel<KERN, DD>), grid, dim3(256), 0, c->stream, p, c->Xt, c->invp, zvec,   \
-                       Minv, c->Npad, partial, tb);                                                              \
-    break;
-  switch (p.d) {
-    CASE_D(1) CASE_D(2) CASE_D(3) CASE_D(4) CASE_D(5) CASE_D(6) CASE_D(7) CASE_D(8)
-    CASE_D(9) CASE_D(10) CASE_D(11) CASE_D(12) CASE_D(13) CASE_D(14) CASE_D(15) CASE_D(16)
-  }
-#undef CASE_D
 }
 
 }  // namespace
@@ -391,9 +356,10 @@ void gpg_launch_grad_contract(gpg_ctx* c, const AsmParams& p_in, double* partial
   if (c->grad_eta >= 0.0) p.eta = c->grad_eta;   // the reference differentiates with self._etaK whatever nugget the matrix got
   const int tb = grad_tb(p.n);
   dim3 grid((p.n + 255) / 256, (p.n + tb - 1) / tb);
-  if (p.kernel == GPG_KERNEL_SQEXP) launch_contract_d<GPG_KERNEL_SQEXP>(c, p, partial, grid, zvec, Minv, tb);
-  else if (p.kernel == GPG_KERNEL_RATQU) launch_contract_d<GPG_KERNEL_RATQU>(c, p, partial, grid, zvec, Minv, tb);
-  else launch_contract_d<GPG_KERNEL_MA5F2>(c, p, partial, grid, zvec, Minv, tb);
+  gpg_for_kern_d(p.kernel, p.d, [&](auto K, auto D) {
+    hipLaunchKernelGGL((grad_contract_kernel<decltype(K)::value, decltype(D)::value>), grid, dim3(256), 0, c->stream, p, c->Xt, c->invp,
+                       zvec, Minv, c->Npad, partial, tb);
+  });
   const int ns = p.d + 3 + (p.kernel == GPG_KERNEL_RATQU ? 1 : 0);
   hipLaunchKernelGGL(grad_final_reduce_kernel, dim3(2 * ns), dim3(64), 0, c->stream, partial, (int)(grid.x * grid.y),
                      2 * ns, out_dev);

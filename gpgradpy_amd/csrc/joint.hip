@@ -13,6 +13,8 @@
 #include <cstring>
 #include <vector>
 #include "gpg_internal.h"
+#include "device_util.h"
+#include "kernel_fn.h"
 
 namespace {
 
@@ -35,24 +37,11 @@ __global__ void __launch_bounds__(256) cross_joint_kernel(AsmParams P, const dou
   if (a_ll >= P.n || j >= nx) return;
   const int a = (int)a_ll, n = P.n, ng = P.ng;
   const int nblk = P.use_grad ? D + 1 : 1;
-  double R[D], th[D], E, M1 = 0.0, K00, s = 0.0;
-  const double sqrt5 = sqrt(5.0);
+  double R[D], th[D], s = 0.0;
 #pragma unroll
-  for (int i = 0; i < D; ++i) { th[i] = P.theta[i]; R[i] = Xt[(size_t)i * n + a] - Xq[(size_t)i * mp + j]; s += th[i] * (R[i] * R[i]); }
-  if (KERN == GPG_KERNEL_SQEXP) {
-    E = exp(-s);
-    K00 = E;
-  } else if (KERN == GPG_KERNEL_RATQU) {
-    const double Bq = 1.0 + s / P.hp_kernel;
-    K00 = pow(Bq, -P.hp_kernel);
-    M1 = pow(Bq, -P.hp_kernel - 1.0);
-    E = pow(Bq, -P.hp_kernel - 2.0);
-  } else {
-    const double nu = sqrt(s);
-    E = exp(-sqrt5 * nu);
-    M1 = ((5.0 / 3.0) * (1.0 + sqrt5 * nu)) * E;
-    K00 = (1.0 + sqrt5 * nu + (5.0 / 3.0) * (nu * nu)) * E;
-  }
+  for (int i = 0; i < D; ++i) { th[i] = P.theta[i]; R[i] = Xt[(size_t)i * n + a] - Xq[(size_t)i * mp + j]; kern_s_add<KERN, false>(s, th[i], R[i]); }
+  const KernRadial rad = kern_radial<KERN>(s, P.hp_kernel);
+  const double E = rad.E, M1 = rad.M1, K00 = rad.K00;
   {   // value column of training point a
     const double ip = invp[a];
     double* w = Wt + (size_t)a * mp + j;
@@ -60,8 +49,7 @@ __global__ void __launch_bounds__(256) cross_joint_kernel(AsmParams P, const dou
     if (qblk > 1) {
 #pragma unroll
       for (int jp = 0; jp < D; ++jp)
-        w[(size_t)(jp + 1) * nx] = ip * (KERN == GPG_KERNEL_SQEXP ? ((2.0 * th[jp]) * R[jp]) * E
-                                         : KERN == GPG_KERNEL_RATQU ? ((2.0 * th[jp]) * R[jp]) * M1 : (th[jp] * R[jp]) * M1);
+        w[(size_t)(jp + 1) * nx] = ip * kern_d01<KERN>(th[jp], R[jp], E, M1);
     }
   }
   const int gpa = P.gpos[a];
@@ -71,38 +59,14 @@ __global__ void __launch_bounds__(256) cross_joint_kernel(AsmParams P, const dou
       const size_t c = (size_t)n + (size_t)i * ng + gpa;
       const double ip = invp[c];
       double* w = Wt + c * mp + j;
-      double v0;
-      if (KERN == GPG_KERNEL_SQEXP) v0 = ((-2.0 * th[i]) * R[i]) * E;
-      else if (KERN == GPG_KERNEL_RATQU) v0 = ((-2.0 * th[i]) * R[i]) * M1;
-      else v0 = ((-th[i]) * R[i]) * M1;
-      w[0] = v0 * ip;
+      w[0] = kern_d10<KERN>(th[i], R[i], E, M1) * ip;
       if (qblk > 1) {
 #pragma unroll
-        for (int jp = 0; jp < D; ++jp) {
-          double v;
-          if (KERN == GPG_KERNEL_SQEXP) {
-            v = (i == jp) ? (2.0 * th[i] - (4.0 * (th[i] * th[i])) * (R[i] * R[i])) * E
-                          : ((-4.0 * th[i]) * th[jp]) * ((R[i] * R[jp]) * E);
-          } else if (KERN == GPG_KERNEL_RATQU) {
-            const double rq_c = 4.0 * (1.0 + 1.0 / P.hp_kernel);
-            v = (i == jp) ? (2.0 * th[i]) * M1 - ((rq_c * (th[i] * th[i])) * (R[i] * R[i])) * E
-                          : (((((-rq_c) * th[i]) * th[jp]) * R[i]) * R[jp]) * E;
-          } else {
-            v = (i == jp) ? th[i] * M1 - (((25.0 / 3.0) * (th[i] * th[i])) * (R[i] * R[i])) * E
-                          : (((((-(25.0 / 3.0)) * th[i]) * th[jp]) * R[i]) * R[jp]) * E;
-          }
-          w[(size_t)(jp + 1) * nx] = ip * v;
-        }
+        for (int jp = 0; jp < D; ++jp)
+          w[(size_t)(jp + 1) * nx] = ip * kern_d11<KERN>(i == jp, th[i], th[jp], R[i], R[jp], E, M1, kern_rq_c(P.hp_kernel));
       }
     }
   }
-}
-
-// Neumaier's compensated accumulation (as the mean of gpg_predict: it cancels by ~kappa on ill-conditioned cases)
-__device__ __forceinline__ void kb_add(double& s, double& comp, double x) {
-  const double t = s + x;
-  comp += (fabs(s) >= fabs(x)) ? (s - t) + x : (x - t) + s;
-  s = t;
 }
 
 // partial[q * mp + r] = sum over the columns c of slice q of Wt[c * mp + r] z[c]   (grid = (mp / 64, S))
@@ -230,23 +194,6 @@ __global__ void __launch_bounds__(256) gram_finish_kernel(const double* __restri
   cov[(size_t)col * m + row] = v;
 }
 
-template <int KERN>
-void launch_cross_joint_d(gpg_ctx* c, const AsmParams& p, int nx, int qblk, int mp) {
-  const int nxs = ((nx + 63) / 64) * 64;
-  const long long total = (long long)p.n * nxs;
-  dim3 grid((unsigned)((total + 255) / 256));
-#define CASE_D(DD)                                                                                                  \
-  case DD:                                                                                                          \
-    hipLaunchKernelGGL((cross_joint_kernel<KERN, DD>), grid, dim3(256), 0, c->stream, p, c->Xt, c->xq_dev, nx, nxs, qblk, \
-                       mp, c->invp, c->Wt);                                                                         \
-    break;
-  switch (p.d) {
-    CASE_D(1) CASE_D(2) CASE_D(3) CASE_D(4) CASE_D(5) CASE_D(6) CASE_D(7) CASE_D(8)
-    CASE_D(9) CASE_D(10) CASE_D(11) CASE_D(12) CASE_D(13) CASE_D(14) CASE_D(15) CASE_D(16)
-  }
-#undef CASE_D
-}
-
 // K-chunks of the Gram kernel for mp rows and Npad columns: about 2048 (tile, chunk) workgroups, a function of the shape only.
 // Measured at Npad = 18048 (tools/joint_time.py --splits ... under a kernel trace): 3 tiles 992 us with one chunk, 27 us with 48,
 // 16-17 us with 141 .. 282; 45 tiles 936 / 181 / 143 / 138 / 136 / 177 us with 1 / 12 / 16 / 48 / 96 / 282 chunks; 666 tiles
@@ -264,9 +211,13 @@ size_t round256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 
 // The rows of Kqy P^-1 of nx query points (xq_dev [d x mp]) into Wt, qblk = 1 (values) or d + 1 (values and derivatives) blocks
 void gpg_launch_cross_joint(gpg_ctx* c, const AsmParams& p, int nx, int qblk, int mp) {
-  if (p.kernel == GPG_KERNEL_SQEXP) launch_cross_joint_d<GPG_KERNEL_SQEXP>(c, p, nx, qblk, mp);
-  else if (p.kernel == GPG_KERNEL_RATQU) launch_cross_joint_d<GPG_KERNEL_RATQU>(c, p, nx, qblk, mp);
-  else launch_cross_joint_d<GPG_KERNEL_MA5F2>(c, p, nx, qblk, mp);
+  const int nxs = ((nx + 63) / 64) * 64;
+  const long long total = (long long)p.n * nxs;
+  const dim3 grid((unsigned)((total + 255) / 256));
+  gpg_for_kern_d(p.kernel, p.d, [&](auto K, auto D) {
+    hipLaunchKernelGGL((cross_joint_kernel<decltype(K)::value, decltype(D)::value>), grid, dim3(256), 0, c->stream, p, c->Xt, c->xq_dev, nx,
+                       nxs, qblk, mp, c->invp, c->Wt);
+  });
 }
 
 // slices of the mean reduction: mpart of gpg_launch_joint_mean holds this many times mp doubles

@@ -15,16 +15,15 @@
 //      second_finish_kernel adds the partials in chunk order, subtracts from K0, scales, adds the mean-uncertainty term and
 //      writes both halves of the block;
 //   4. Hessians only: gpg_backward_rows on the tiles that hold the value rows (after step 3 has read them), the mean-uncertainty
-//      update of those rows, second_contract_kernel -- hess_contract_kernel (solve.hip) with a grid over (row k, query point j)
-//      -- and second_hess_kernel, which assembles d2mudx2 and d2sigdx2 by the formulas of gpg_predict_hess;
+//      update of those rows, hess_contract_kernel (solve.hip: gpg_predict_hess runs it for one point) on a grid over
+//      (row k, query point j), and second_hess_kernel, which assembles d2mudx2 and d2sigdx2 by the formulas of gpg_predict_hess;
 //   5. one copy per output and one synchronisation.
 // The K-chunk count is a function of Npad only (or gpg_set_gram_splits): a point's block does not depend on how many points ride
 // along with it.  Ordinary grids, no atomics, no workgroup waits for another: the results are a function of the shape only.
 //
 // Registers of second_gram_kernel (-Rpass-analysis=kernel-resource-usage, gfx950; VGPRs / scratch bytes / waves per SIMD) next to
 // loo_gram_kernel's: G = 5: 62 / 0 / 8 (loo 68 / 0 / 7); G = 9: 126 / 0 / 4 (191 / 0 / 2); groups of 6, diagonal: 66 / 0 / 7 (70 / 0 / 7),
-// off-diagonal: 126 / 0 / 4 (157 / 0 / 3).  No kernel of this file uses scratch (second_contract_kernel takes row k's coordinate
-// through memory and lets thread 0 store the sums: an index that is not a compile-time constant would put the arrays there).
+// off-diagonal: 126 / 0 / 4 (157 / 0 / 3).  No kernel of this file uses scratch.
 // Measured on one MI355X (tools/second_time.py; host clock, median after warm-up, two runs; sweep and Gram from gpg_prof events):
 //   (a) gcov alone at the largest nx gpg_predict_joint takes          n = 2000, d = 8, nx = 455      n = 500, d = 4, nx = 819
 //       gpg_predict_second                                            26.5 - 26.6 ms                 0.87 - 0.88 ms
@@ -46,31 +45,6 @@ namespace {
 constexpr int kSecondMaxRows = 4096;   // rows of a chunk, padded to 64: what Wt is sized for by the other posterior calls as well
 constexpr int kSecondChunksMax = 64;   // K-chunks of the Gram kernel when gpg_set_gram_splits is not set: min(Npad / 64, this)
 constexpr int kSecondGroup = 6;        // block rows per group once bs block rows no longer fit one lane's registers (dim > 8), as loo.hip
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
-// block-wide sum of NV values per thread (as solve.hip); result valid in every thread
-template <int NV>
-__device__ void block_sum(double (&v)[NV], double* sh /* [NV * 16] */) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-#pragma unroll
-  for (int q = 0; q < NV; ++q) {
-    double s = wave_sum(v[q]);
-    if (lane == 0) sh[q * 16 + w] = s;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < NV; ++q) {
-    double s = 0.0;
-    for (int i = 0; i < nw; ++i) s += sh[q * 16 + i];
-    v[q] = s;
-  }
-  __syncthreads();
-}
 
 // partial[(s npairs + p) npad + j] = sum over the columns of K-chunk s of Z[bi pc + j, c] Z[bj pc + j, c], p = bj (bj + 1) / 2 + bi,
 // for the block rows bi <= bj of pair tile blockIdx.z: groups of G block rows, tile (gi, gj) holds the rows [gi G, gi G + G) x
@@ -188,96 +162,6 @@ __global__ void __launch_bounds__(64) second_finish_kernel(SecondFinish f) {
   if (f.sraw) f.sraw[(size_t)p * f.npad + j] = g;
 }
 
-// hess_contract_kernel (solve.hip: the formulas and their order are its own) for every point of a chunk: workgroup (k, j) -> row k of
-// H1_j = sum_c d2K_j[k, :, c] alpha_c and H2_j = sum_c d2K_j[k, :, c] v_j,c, v_j = row j of the backward-swept Z (K^-1 Kyx of
-// point j; with the mean uncertainty K^-1 k + K^-1 V H^-1 u).  h1o, h2o [pc, D, D].  Xq is [D x ldz].
-template <int KERN, int D>
-__global__ void __launch_bounds__(256) second_contract_kernel(AsmParams P, const double* __restrict__ Xt, const double* __restrict__ Xq,
-                                                              int ldz, const double* __restrict__ invp, const double* __restrict__ zvec,
-                                                              const double* __restrict__ Z, double* __restrict__ h1o,
-                                                              double* __restrict__ h2o) {
-  __shared__ double sh[2 * D * 16];
-  const int k = blockIdx.x, jq = blockIdx.y, n = P.n, ng = P.ng;
-  const int nblk = P.use_grad ? D + 1 : 1;
-  double g[2 * D];
-#pragma unroll
-  for (int i = 0; i < 2 * D; ++i) g[i] = 0.0;
-  double xq[D], th[D];
-#pragma unroll
-  for (int i = 0; i < D; ++i) { xq[i] = Xq[(size_t)i * ldz + jq]; th[i] = P.theta[i]; }
-  // row k's own coordinate and theta through memory (k is uniform): indexing xq / th / tR with it would put the arrays in scratch
-  const double xqk = Xq[(size_t)k * ldz + jq], thk = P.theta[k];
-  const double sqrt5 = sqrt(5.0);
-  const double rq_s1 = 1.0 + 1.0 / P.hp_kernel, rq_s2 = rq_s1 * (1.0 + 2.0 / P.hp_kernel);   // RatQu only
-  for (int a = threadIdx.x; a < n; a += 256) {
-    double R[D], tR[D], E, M1 = 0.0, c3 = 0.0, F3 = 0.0;
-    double s = 0.0;
-#pragma unroll
-    for (int i = 0; i < D; ++i) { R[i] = Xt[(size_t)i * n + a] - xq[i]; tR[i] = th[i] * R[i]; s += tR[i] * R[i]; }
-    if (KERN == GPG_KERNEL_SQEXP) {
-      E = exp(-s);
-    } else if (KERN == GPG_KERNEL_RATQU) {               // f_p = B^(-alpha-p): M1 = f_1, E = f_2, F3 = f_3
-      const double Bq = 1.0 + s / P.hp_kernel;
-      M1 = pow(Bq, -P.hp_kernel - 1.0);
-      E = pow(Bq, -P.hp_kernel - 2.0);
-      F3 = pow(Bq, -P.hp_kernel - 3.0);
-    } else {
-      const double nu = sqrt(s);
-      E = exp(-sqrt5 * nu);
-      M1 = ((5.0 / 3.0) * (1.0 + sqrt5 * nu)) * E;
-      c3 = sqrt5 / fmax(nu, 1e-16);
-    }
-    const double tRk = thk * (Xt[(size_t)k * n + a] - xqk);   // = tR[k], the same two operations
-    {
-      const double wa = zvec[a] * invp[a], ws = Z[(size_t)a * ldz + jq] * invp[a];
-#pragma unroll
-      for (int i = 0; i < D; ++i) {
-        double v;
-        if (KERN == GPG_KERNEL_SQEXP) v = (4.0 * tR[i] * tRk - (i == k ? 2.0 * th[i] : 0.0)) * E;
-        else if (KERN == GPG_KERNEL_RATQU) v = (4.0 * rq_s1) * tR[i] * tRk * E - (i == k ? 2.0 * th[i] * M1 : 0.0);
-        else v = (25.0 / 3.0) * tR[i] * tRk * E - (i == k ? thk * M1 : 0.0);
-        g[i] += v * wa;
-        g[D + i] += v * ws;
-      }
-    }
-    const int gpa = P.gpos[a];
-    if (nblk > 1 && gpa >= 0) {
-#pragma unroll
-      for (int j = 0; j < D; ++j) {
-        const size_t c = (size_t)n + (size_t)j * ng + gpa;
-        const double ip = invp[c];
-        const double wa = zvec[c] * ip, ws = Z[c * ldz + jq] * ip;
-#pragma unroll
-        for (int i = 0; i < D; ++i) {
-          double v;
-          if (KERN == GPG_KERNEL_SQEXP) {
-            v = 4.0 * ((i == k ? th[i] * tR[j] : 0.0) + (j == k ? th[j] * tR[i] : 0.0) + (i == j ? th[i] * tRk : 0.0))
-                - 8.0 * tR[i] * tR[j] * tRk;
-            v *= E;
-          } else if (KERN == GPG_KERNEL_RATQU) {
-            v = (4.0 * rq_s1) * ((i == k ? th[i] * tR[j] : 0.0) + (j == k ? th[j] * tR[i] : 0.0) + (i == j ? th[i] * tRk : 0.0)) * E
-                - (8.0 * rq_s2) * tR[i] * tR[j] * tRk * F3;
-          } else {
-            v = (i == k ? th[i] * tR[j] : 0.0) + (j == k ? th[j] * tR[i] : 0.0) + (i == j ? th[i] * tRk : 0.0)
-                - c3 * tR[i] * tR[j] * tRk;
-            v *= (25.0 / 3.0) * E;
-          }
-          g[i] += v * wa;
-          g[D + i] += v * ws;
-        }
-      }
-    }
-  }
-  block_sum<2 * D>(g, sh);
-  if (threadIdx.x == 0) {   // (an index that differs by lane would put g in scratch for the whole loop)
-#pragma unroll
-    for (int i = 0; i < D; ++i) {
-      h1o[((size_t)jq * D + k) * D + i] = g[i];
-      h2o[((size_t)jq * D + k) * D + i] = g[D + i];
-    }
-  }
-}
-
 // Thread <-> (point j, k, i): d2mudx2 = H1 and, by the arithmetic of gpg_predict_hess with sig and dsigdx taken from the block,
 //   sig = sqrt(max(0, gcov_00)),  dsigdx_k = gcov_0,k+1 / sig,  d2sig2 = -2 varK (H2 + T) (+ 2 varK c'_k+1 . c'_i+1),
 //   d2sigdx2 = (d2sig2 - 2 dsigdx_k dsigdx_i) / (2 sig),  NaN where sig == 0.
@@ -303,20 +187,6 @@ __global__ void __launch_bounds__(256) second_hess_kernel(int pc, int d, int npa
   }
   const double dsk = blk[1 + k] / sg, dsi = blk[1 + i] / sg;
   d2sig[t] = sg != 0.0 ? (d2s2 - 2.0 * dsk * dsi) / (2.0 * sg) : __longlong_as_double(0x7ff8000000000000LL);
-}
-
-template <int KERN>
-void launch_contract_d(gpg_ctx* c, const AsmParams& p, int pc, int ldz, double* h1, double* h2) {
-#define CASE_D(DD)                                                                                                          \
-  case DD:                                                                                                                  \
-    hipLaunchKernelGGL((second_contract_kernel<KERN, DD>), dim3(DD, pc), dim3(256), 0, c->stream, p, c->Xt, c->xq_dev, ldz, \
-                       c->invp, c->zvec, c->Wt, h1, h2);                                                                    \
-    break;
-  switch (p.d) {
-    CASE_D(1) CASE_D(2) CASE_D(3) CASE_D(4) CASE_D(5) CASE_D(6) CASE_D(7) CASE_D(8)
-    CASE_D(9) CASE_D(10) CASE_D(11) CASE_D(12) CASE_D(13) CASE_D(14) CASE_D(15) CASE_D(16)
-  }
-#undef CASE_D
 }
 
 // K-chunks of second_gram_kernel: a function of Npad only (never of nx or of the points per chunk), or what gpg_set_gram_splits asks for
@@ -449,9 +319,7 @@ int predict_second_once(gpg_ctx* c, int nx, const double* xq, double varK, doubl
       // along: the Gram kernel has read them)
       gpg_backward_rows(c, c->Wt, mp, std::min(npad, m), c->gradbuf + (size_t)2 * mp * GPG_MAX_DIM);
       if (munc) gpg_meanunc_update_rows(c, c->Wt, mp, pc);
-      if (p.kernel == GPG_KERNEL_SQEXP) launch_contract_d<GPG_KERNEL_SQEXP>(c, p, pc, mp, h1, h2);
-      else if (p.kernel == GPG_KERNEL_RATQU) launch_contract_d<GPG_KERNEL_RATQU>(c, p, pc, mp, h1, h2);
-      else launch_contract_d<GPG_KERNEL_MA5F2>(c, p, pc, mp, h1, h2);
+      gpg_launch_hess_contract(c, p, pc, mp, h1, h2);
       const int total = pc * d * d;
       hipLaunchKernelGGL(second_hess_kernel, dim3((total + 255) / 256), dim3(256), 0, c->stream, pc, d, npad, mp, nb, munc ? 1 : 0, varK,
                          (const double*)h1, (const double*)h2, (const double*)sraw, (const double*)blk_dev,

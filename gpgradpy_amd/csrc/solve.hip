@@ -7,33 +7,10 @@
 //   extract         : dense N x N copies on request (tests / drop-in 7-tuple)
 #include <algorithm>
 #include "gpg_internal.h"
+#include "device_util.h"
+#include "kernel_fn.h"
 
 namespace {
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
-// block-wide sum of NV values per thread; result valid in every thread
-template <int NV>
-__device__ void block_sum(double (&v)[NV], double* sh /* [NV * 16] */) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-#pragma unroll
-  for (int q = 0; q < NV; ++q) {
-    double s = wave_sum(v[q]);
-    if (lane == 0) sh[q * 16 + w] = s;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < NV; ++q) {
-    double s = 0.0;
-    for (int i = 0; i < nw; ++i) s += sh[q * 16 + i];
-    v[q] = s;
-  }
-  __syncthreads();
-}
 
 // orders the LDS accesses of ONE wave across a step of a wave-local algorithm (no workgroup barrier: the other waves are not involved)
 __device__ __forceinline__ void wave_lds_sync() {
@@ -243,15 +220,6 @@ __global__ void alpha_kernel(const double* __restrict__ z, const double* __restr
   if (r < N) alpha[r] = z[r] * invp[r];
 }
 
-// Neumaier's compensated accumulation: s + comp carries the sum to ~eps |result| + eps^2 sum |terms|.  The mean
-// mu = beta + sum_c Wt[j, c] z[c] cancels by a factor ~kappa on ill-conditioned cases (|alpha| ~ kappa |mu|), so the
-// order of a plain summation shows up at eps kappa (measured 4e-8 .. 2e-7 at kappa = 7e9 depending on the slicing).
-__device__ __forceinline__ void kb_add(double& s, double& comp, double x) {
-  const double t = s + x;
-  comp += (fabs(s) >= fabs(x)) ? (s - t) + x : (x - t) + s;
-  s = t;
-}
-
 // prior mean at query j: the constant beta, or with a first-order mean (betav != nullptr, device [d + 1]; Xq [d x nxp])
 // beta_0 + xq_j . beta_1..d (GpMeanFun.py:14-67)
 __device__ __forceinline__ double prior_mean(double beta, const double* __restrict__ betav, const double* __restrict__ Xq, int d, int nxp,
@@ -388,38 +356,20 @@ __global__ void __launch_bounds__(256) cross_grad_kernel(AsmParams P, const doub
   double xq[D], th[D];
 #pragma unroll
   for (int k = 0; k < D; ++k) { xq[k] = Xq[(size_t)k * nxp + q]; th[k] = P.theta[k]; }
-  const double sqrt5 = sqrt(5.0);
-  const double rq_const = 4.0 * (1.0 + 1.0 / P.hp_kernel);       // KernelRatQuad.py:529 (unused by the other kernels)
+  const double rq_c = kern_rq_c(P.hp_kernel);
   for (int a = threadIdx.x; a < n; a += 256) {
-    double R[D], E, M1 = 0.0;
-    if (KERN == GPG_KERNEL_SQEXP) {
-      double s = 0.0;
+    double R[D], s = 0.0;
 #pragma unroll
-      for (int k = 0; k < D; ++k) { R[k] = Xt[(size_t)k * n + a] - xq[k]; s -= th[k] * (R[k] * R[k]); }
-      E = exp(s);
-    } else if (KERN == GPG_KERNEL_RATQU) {       // KernelRatQuad.py:463-476: M1 = B^(-alpha-1), E <- B^(-alpha-2)
-      double s = 0.0;
-#pragma unroll
-      for (int k = 0; k < D; ++k) { R[k] = Xt[(size_t)k * n + a] - xq[k]; s += th[k] * (R[k] * R[k]); }
-      const double Bq = 1.0 + s / P.hp_kernel;
-      M1 = pow(Bq, -P.hp_kernel - 1.0);
-      E = pow(Bq, -P.hp_kernel - 2.0);
-    } else {
-      double s = 0.0;
-#pragma unroll
-      for (int k = 0; k < D; ++k) { R[k] = Xt[(size_t)k * n + a] - xq[k]; s += th[k] * (R[k] * R[k]); }
-      const double nu = sqrt(s);
-      E = exp(-sqrt5 * nu);
-      M1 = ((5.0 / 3.0) * (1.0 + sqrt5 * nu)) * E;
-    }
+    for (int k = 0; k < D; ++k) { R[k] = Xt[(size_t)k * n + a] - xq[k]; kern_s_add<KERN, true>(s, th[k], R[k]); }
+    const KernRadial rad = kern_radial<KERN, true>(s, P.hp_kernel);
+    const double E = rad.E, M1 = rad.M1;
     const int gpa = P.gpos[a];
-    // I = 0 : block (0, j'+1) = +2 th R E  (SqExp) / + th R mat1 (Matern)
+    // I = 0 : block (0, j'+1)
     {
       const double wa = zvec[a] * invp[a], ws = Z[(size_t)a * nxp + q] * invp[a];
 #pragma unroll
       for (int jp = 0; jp < D; ++jp) {
-        const double v = KERN == GPG_KERNEL_SQEXP ? ((2.0 * th[jp]) * R[jp]) * E
-                         : KERN == GPG_KERNEL_RATQU ? ((2.0 * th[jp]) * R[jp]) * M1 : (th[jp] * R[jp]) * M1;   // RatQu: :541
+        const double v = kern_d01<KERN>(th[jp], R[jp], E, M1);
         g[jp] += v * wa;
         g[D + jp] += v * ws;
       }
@@ -432,17 +382,7 @@ __global__ void __launch_bounds__(256) cross_grad_kernel(AsmParams P, const doub
         const double wa = zvec[c] * ip, ws = Z[c * nxp + q] * ip;
 #pragma unroll
         for (int jp = 0; jp < D; ++jp) {
-          double v;
-          if (KERN == GPG_KERNEL_SQEXP) {
-            v = (i == jp) ? (2.0 * th[i] - (4.0 * (th[i] * th[i])) * (R[i] * R[i])) * E
-                          : ((-4.0 * th[i]) * th[jp]) * ((R[i] * R[jp]) * E);
-          } else if (KERN == GPG_KERNEL_RATQU) {     // KernelRatQuad.py:544, 554
-            v = (i == jp) ? (2.0 * th[i]) * M1 - ((rq_const * (th[i] * th[i])) * (R[i] * R[i])) * E
-                          : (((((-rq_const) * th[i]) * th[jp]) * R[i]) * R[jp]) * E;
-          } else {
-            v = (i == jp) ? th[i] * M1 - (((25.0 / 3.0) * (th[i] * th[i])) * (R[i] * R[i])) * E
-                          : (((((-(25.0 / 3.0)) * th[i]) * th[jp]) * R[i]) * R[jp]) * E;
-          }
+          const double v = kern_d11<KERN>(i == jp, th[i], th[jp], R[i], R[jp], E, M1, rq_c);
           g[jp] += v * wa;
           g[D + jp] += v * ws;
         }
@@ -457,76 +397,43 @@ __global__ void __launch_bounds__(256) cross_grad_kernel(AsmParams P, const doub
   }
 }
 
-template <int KERN>
-void launch_cross_grad_d(gpg_ctx* c, const AsmParams& p, int nx, int nxp, double* g1, double* g2) {
-#define CASE_D(DD)                                                                                          \
-  case DD:                                                                                                  \
-    hipLaunchKernelGGL((cross_grad_kernel<KERN, DD>), dim3(nx), dim3(256), 0, c->stream, p, c->Xt, c->xq_dev, nxp, \
-                       c->invp, c->zvec, c->Wt, g1, g2, c->eval_linear ? c->eval_beta_dev : (const double*)nullptr); \
-    break;
-  switch (p.d) {
-    CASE_D(1) CASE_D(2) CASE_D(3) CASE_D(4) CASE_D(5) CASE_D(6) CASE_D(7) CASE_D(8)
-    CASE_D(9) CASE_D(10) CASE_D(11) CASE_D(12) CASE_D(13) CASE_D(14) CASE_D(15) CASE_D(16)
-  }
-#undef CASE_D
-}
-
 // ------------------------------------------------------------------------------------------------
-// Posterior Hessians at ONE query point (reference GpEvalModel.py:355-382, kernel second / third derivatives
-// KernelSqExp.py:48-88,412-468, KernelMatern5f2.py:54-94,453-530).  With R = x_a - xq (this file's sign):
-//   base column a          : d2K[k,i] = (-2 th_i d_ik + 4 th_i th_k R_i R_k) E                     (SqExp)
-//                                       -th_k M1 d_ik + (25/3) th_i R_i th_k R_k E                 (Matern 5/2)
-//   gradient column (j, a) : d2K[k,i] = (4 th_i th_j (d_ik R_j + d_jk R_i) + 4 d_ij th_i th_k R_k
-//                                        - 8 th_i th_j th_k R_i R_j R_k) E                          (SqExp)
-//                                       (25/3) (th_i d_ik th_j R_j + th_j d_jk th_i R_i + th_i d_ij th_k R_k
-//                                        - sqrt5 / nu th_i R_i th_j R_j th_k R_k) E                 (Matern 5/2)
-// hess_contract_kernel: workgroup k -> row k of  H1 = sum_c d2K[k,:,c] alpha_c  and  H2 = sum_c d2K[k,:,c] v_c,
-// v = K^-1 Kyx (row 0 of Z).  Nothing of the [d, d, N] tensor is stored.
+// Posterior Hessians (reference GpEvalModel.py:355-382; the kernel second / third derivatives d2K are kern_d2k_base and
+// kern_d2k_grad of kernel_fn.h, with R = x_a - xq, this file's sign).
+// hess_contract_kernel: workgroup (k, j) -> row k of  H1_j = sum_c d2K_j[k,:,c] alpha_c  and  H2_j = sum_c d2K_j[k,:,c] v_j,c  for
+// query point j of the grid (gpg_predict_hess: one; gpg_predict_second: the points of a chunk), v_j = K^-1 Kyx of point j = row j
+// of the backward-swept Z (with the mean uncertainty K^-1 k + K^-1 V H^-1 u).  h1o, h2o [points, D, D].  Xq is [D x ldz].
+// Nothing of the [d, d, N] tensor is stored.
 // ------------------------------------------------------------------------------------------------
 template <int KERN, int D>
-__global__ void __launch_bounds__(256) hess_contract_kernel(AsmParams P, const double* __restrict__ Xt,
-                                                            const double* __restrict__ Xq, int nxp,
-                                                            const double* __restrict__ invp, const double* __restrict__ zvec,
-                                                            const double* __restrict__ Z, double* __restrict__ h1o,
-                                                            double* __restrict__ h2o) {
+__global__ void __launch_bounds__(256) hess_contract_kernel(AsmParams P, const double* __restrict__ Xt, const double* __restrict__ Xq,
+                                                              int ldz, const double* __restrict__ invp, const double* __restrict__ zvec,
+                                                              const double* __restrict__ Z, double* __restrict__ h1o,
+                                                              double* __restrict__ h2o) {
   __shared__ double sh[2 * D * 16];
-  const int k = blockIdx.x, n = P.n, ng = P.ng;
+  const int k = blockIdx.x, jq = blockIdx.y, n = P.n, ng = P.ng;
   const int nblk = P.use_grad ? D + 1 : 1;
   double g[2 * D];
 #pragma unroll
   for (int i = 0; i < 2 * D; ++i) g[i] = 0.0;
   double xq[D], th[D];
 #pragma unroll
-  for (int i = 0; i < D; ++i) { xq[i] = Xq[(size_t)i * nxp]; th[i] = P.theta[i]; }
-  const double sqrt5 = sqrt(5.0);
+  for (int i = 0; i < D; ++i) { xq[i] = Xq[(size_t)i * ldz + jq]; th[i] = P.theta[i]; }
+  // row k's own coordinate and theta through memory (k is uniform): indexing xq / th / tR with it would put the arrays in scratch
+  const double xqk = Xq[(size_t)k * ldz + jq], thk = P.theta[k];
   const double rq_s1 = 1.0 + 1.0 / P.hp_kernel, rq_s2 = rq_s1 * (1.0 + 2.0 / P.hp_kernel);   // RatQu only
   for (int a = threadIdx.x; a < n; a += 256) {
-    double R[D], tR[D], E, M1 = 0.0, c3 = 0.0, F3 = 0.0;
+    double R[D], tR[D];
     double s = 0.0;
 #pragma unroll
     for (int i = 0; i < D; ++i) { R[i] = Xt[(size_t)i * n + a] - xq[i]; tR[i] = th[i] * R[i]; s += tR[i] * R[i]; }
-    if (KERN == GPG_KERNEL_SQEXP) {
-      E = exp(-s);
-    } else if (KERN == GPG_KERNEL_RATQU) {               // f_p = B^(-alpha-p): M1 = f_1, E = f_2, F3 = f_3
-      const double Bq = 1.0 + s / P.hp_kernel;
-      M1 = pow(Bq, -P.hp_kernel - 1.0);
-      E = pow(Bq, -P.hp_kernel - 2.0);
-      F3 = pow(Bq, -P.hp_kernel - 3.0);
-    } else {
-      const double nu = sqrt(s);
-      E = exp(-sqrt5 * nu);
-      M1 = ((5.0 / 3.0) * (1.0 + sqrt5 * nu)) * E;
-      c3 = sqrt5 / fmax(nu, 1e-16);                      // KernelMatern5f2.py:500
-    }
-    const double tRk = tR[k];
+    const KernRadial rad = kern_radial<KERN>(s, P.hp_kernel);
+    const double tRk = thk * (Xt[(size_t)k * n + a] - xqk);   // = tR[k], the same two operations
     {
-      const double wa = zvec[a] * invp[a], ws = Z[(size_t)a * nxp] * invp[a];
+      const double wa = zvec[a] * invp[a], ws = Z[(size_t)a * ldz + jq] * invp[a];
 #pragma unroll
       for (int i = 0; i < D; ++i) {
-        double v;
-        if (KERN == GPG_KERNEL_SQEXP) v = (4.0 * tR[i] * tRk - (i == k ? 2.0 * th[i] : 0.0)) * E;
-        else if (KERN == GPG_KERNEL_RATQU) v = (4.0 * rq_s1) * tR[i] * tRk * E - (i == k ? 2.0 * th[i] * M1 : 0.0);   // KernelRatQuad.py:51-136
-        else v = (25.0 / 3.0) * tR[i] * tRk * E - (i == k ? th[k] * M1 : 0.0);
+        const double v = kern_d2k_base<KERN>(i, k, th[i], thk, tR[i], tRk, rad.E, rad.M1, rq_s1);
         g[i] += v * wa;
         g[D + i] += v * ws;
       }
@@ -537,22 +444,10 @@ __global__ void __launch_bounds__(256) hess_contract_kernel(AsmParams P, const d
       for (int j = 0; j < D; ++j) {
         const size_t c = (size_t)n + (size_t)j * ng + gpa;
         const double ip = invp[c];
-        const double wa = zvec[c] * ip, ws = Z[c * nxp] * ip;
+        const double wa = zvec[c] * ip, ws = Z[c * ldz + jq] * ip;
 #pragma unroll
         for (int i = 0; i < D; ++i) {
-          double v;
-          if (KERN == GPG_KERNEL_SQEXP) {
-            v = 4.0 * ((i == k ? th[i] * tR[j] : 0.0) + (j == k ? th[j] * tR[i] : 0.0) + (i == j ? th[i] * tRk : 0.0))
-                - 8.0 * tR[i] * tR[j] * tRk;
-            v *= E;
-          } else if (KERN == GPG_KERNEL_RATQU) {           // KernelRatQuad.py:556-632
-            v = (4.0 * rq_s1) * ((i == k ? th[i] * tR[j] : 0.0) + (j == k ? th[j] * tR[i] : 0.0) + (i == j ? th[i] * tRk : 0.0)) * E
-                - (8.0 * rq_s2) * tR[i] * tR[j] * tRk * F3;
-          } else {
-            v = (i == k ? th[i] * tR[j] : 0.0) + (j == k ? th[j] * tR[i] : 0.0) + (i == j ? th[i] * tRk : 0.0)
-                - c3 * tR[i] * tR[j] * tRk;
-            v *= (25.0 / 3.0) * E;
-          }
+          const double v = kern_d2k_grad<KERN>(i, j, k, th[i], th[j], tR[i], tR[j], tRk, rad.E, rad.F3, rad.c3, rq_s1, rq_s2);
           g[i] += v * wa;
           g[D + i] += v * ws;
         }
@@ -560,9 +455,12 @@ __global__ void __launch_bounds__(256) hess_contract_kernel(AsmParams P, const d
     }
   }
   block_sum<2 * D>(g, sh);
-  if (threadIdx.x < D) {
-    h1o[(size_t)k * D + threadIdx.x] = g[threadIdx.x];
-    h2o[(size_t)k * D + threadIdx.x] = g[D + threadIdx.x];
+  if (threadIdx.x == 0) {   // (an index that differs by lane would put g in scratch for the whole loop)
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+      h1o[((size_t)jq * D + k) * D + i] = g[i];
+      h2o[((size_t)jq * D + k) * D + i] = g[D + i];
+    }
   }
 }
 
@@ -576,28 +474,17 @@ __global__ void __launch_bounds__(256) cross_dx_rows_kernel(AsmParams P, const d
   const int a = blockIdx.x * 256 + threadIdx.x, n = P.n, ng = P.ng;
   if (a >= n) return;
   const int nblk = P.use_grad ? D + 1 : 1;
-  double R[D], th[D], E, M1 = 0.0, s = 0.0;
-  const double sqrt5 = sqrt(5.0);
+  double R[D], th[D], s = 0.0;
 #pragma unroll
-  for (int i = 0; i < D; ++i) { th[i] = P.theta[i]; R[i] = Xt[(size_t)i * n + a] - Xq[(size_t)i * nxp]; s += th[i] * (R[i] * R[i]); }
-  if (KERN == GPG_KERNEL_SQEXP) {
-    E = exp(-s);
-  } else if (KERN == GPG_KERNEL_RATQU) {
-    const double Bq = 1.0 + s / P.hp_kernel;
-    M1 = pow(Bq, -P.hp_kernel - 1.0);
-    E = pow(Bq, -P.hp_kernel - 2.0);
-  } else {
-    const double nu = sqrt(s);
-    E = exp(-sqrt5 * nu);
-    M1 = ((5.0 / 3.0) * (1.0 + sqrt5 * nu)) * E;
-  }
+  for (int i = 0; i < D; ++i) { th[i] = P.theta[i]; R[i] = Xt[(size_t)i * n + a] - Xq[(size_t)i * nxp]; kern_s_add<KERN, false>(s, th[i], R[i]); }
+  const KernRadial rad = kern_radial<KERN>(s, P.hp_kernel);
+  const double E = rad.E, M1 = rad.M1;
   {
     const double ip = invp[a];
     Wt[(size_t)a * nxp] = 0.0;
 #pragma unroll
     for (int jp = 0; jp < D; ++jp)
-      Wt[(size_t)a * nxp + 1 + jp] = ip * (KERN == GPG_KERNEL_SQEXP ? ((2.0 * th[jp]) * R[jp]) * E
-                                          : KERN == GPG_KERNEL_RATQU ? ((2.0 * th[jp]) * R[jp]) * M1 : (th[jp] * R[jp]) * M1);
+      Wt[(size_t)a * nxp + 1 + jp] = ip * kern_d01<KERN>(th[jp], R[jp], E, M1);
   }
   const int gpa = P.gpos[a];
   if (nblk > 1 && gpa >= 0) {
@@ -607,21 +494,8 @@ __global__ void __launch_bounds__(256) cross_dx_rows_kernel(AsmParams P, const d
       const double ip = invp[c];
       Wt[c * nxp] = 0.0;
 #pragma unroll
-      for (int jp = 0; jp < D; ++jp) {
-        double v;
-        if (KERN == GPG_KERNEL_SQEXP) {
-          v = (i == jp) ? (2.0 * th[i] - (4.0 * (th[i] * th[i])) * (R[i] * R[i])) * E
-                        : ((-4.0 * th[i]) * th[jp]) * ((R[i] * R[jp]) * E);
-        } else if (KERN == GPG_KERNEL_RATQU) {
-          const double rq_c = 4.0 * (1.0 + 1.0 / P.hp_kernel);
-          v = (i == jp) ? (2.0 * th[i]) * M1 - ((rq_c * (th[i] * th[i])) * (R[i] * R[i])) * E
-                        : (((((-rq_c) * th[i]) * th[jp]) * R[i]) * R[jp]) * E;
-        } else {
-          v = (i == jp) ? th[i] * M1 - (((25.0 / 3.0) * (th[i] * th[i])) * (R[i] * R[i])) * E
-                        : (((((-(25.0 / 3.0)) * th[i]) * th[jp]) * R[i]) * R[jp]) * E;
-        }
-        Wt[c * nxp + 1 + jp] = ip * v;
-      }
+      for (int jp = 0; jp < D; ++jp)
+        Wt[c * nxp + 1 + jp] = ip * kern_d11<KERN>(i == jp, th[i], th[jp], R[i], R[jp], E, M1, kern_rq_c(P.hp_kernel));
     }
   }
 }
@@ -643,26 +517,6 @@ __global__ void __launch_bounds__(256) rows_gram_kernel(const double* __restrict
   }
   block_sum<D>(g, sh);
   if (threadIdx.x < D) T[(size_t)i * D + threadIdx.x] = g[threadIdx.x];
-}
-
-template <int KERN>
-void launch_hess_d(gpg_ctx* c, const AsmParams& p, int nxp, double* h1, double* h2, double* T, int stage) {
-#define CASE_D(DD)                                                                                                   \
-  case DD:                                                                                                           \
-    if (stage == 0)                                                                                                  \
-      hipLaunchKernelGGL((hess_contract_kernel<KERN, DD>), dim3(DD), dim3(256), 0, c->stream, p, c->Xt, c->xq_dev, nxp,  \
-                         c->invp, c->zvec, c->Wt, h1, h2);                                                           \
-    else if (stage == 1)                                                                                             \
-      hipLaunchKernelGGL((cross_dx_rows_kernel<KERN, DD>), dim3((p.n + 255) / 256), dim3(256), 0, c->stream, p, c->Xt,   \
-                         c->xq_dev, nxp, c->invp, c->Wt);                                                            \
-    else                                                                                                             \
-      hipLaunchKernelGGL((rows_gram_kernel<DD>), dim3(DD), dim3(256), 0, c->stream, c->Wt, nxp, c->Npad, T);          \
-    break;
-  switch (p.d) {
-    CASE_D(1) CASE_D(2) CASE_D(3) CASE_D(4) CASE_D(5) CASE_D(6) CASE_D(7) CASE_D(8)
-    CASE_D(9) CASE_D(10) CASE_D(11) CASE_D(12) CASE_D(13) CASE_D(14) CASE_D(15) CASE_D(16)
-  }
-#undef CASE_D
 }
 
 // which 0..2: symmetric copy of the lower triangle; which 3: P L (lower), zeros above
@@ -756,16 +610,31 @@ void gpg_backward_rows(gpg_ctx* c, double* Z, int ldz, int nrhs, double* tbuf) {
 }
 
 void gpg_launch_cross_grad(gpg_ctx* c, const AsmParams& p, int nx, int nxp, double* g1, double* g2) {
-  if (p.kernel == GPG_KERNEL_SQEXP) launch_cross_grad_d<GPG_KERNEL_SQEXP>(c, p, nx, nxp, g1, g2);
-  else if (p.kernel == GPG_KERNEL_RATQU) launch_cross_grad_d<GPG_KERNEL_RATQU>(c, p, nx, nxp, g1, g2);
-  else launch_cross_grad_d<GPG_KERNEL_MA5F2>(c, p, nx, nxp, g1, g2);
+  gpg_for_kern_d(p.kernel, p.d, [&](auto K, auto D) {
+    hipLaunchKernelGGL((cross_grad_kernel<decltype(K)::value, decltype(D)::value>), dim3(nx), dim3(256), 0, c->stream, p, c->Xt, c->xq_dev,
+                       nxp, c->invp, c->zvec, c->Wt, g1, g2, c->eval_linear ? c->eval_beta_dev : (const double*)nullptr);
+  });
 }
 
-// stage 0: H1 / H2 contraction, 1: derivative rows into Wt rows 1..d, 2: Gram of those rows after the forward sweep
-void gpg_launch_hess_stage(gpg_ctx* c, const AsmParams& p, int nxp, double* h1, double* h2, double* T, int stage) {
-  if (p.kernel == GPG_KERNEL_SQEXP) launch_hess_d<GPG_KERNEL_SQEXP>(c, p, nxp, h1, h2, T, stage);
-  else if (p.kernel == GPG_KERNEL_RATQU) launch_hess_d<GPG_KERNEL_RATQU>(c, p, nxp, h1, h2, T, stage);
-  else launch_hess_d<GPG_KERNEL_MA5F2>(c, p, nxp, h1, h2, T, stage);
+// H1 / H2 of the pc query points in xq_dev [d x ldz], their K^-1 Kyx in rows 0 .. pc - 1 of Wt (leading dimension ldz): h1, h2 [pc, d, d]
+void gpg_launch_hess_contract(gpg_ctx* c, const AsmParams& p, int pc, int ldz, double* h1, double* h2) {
+  gpg_for_kern_d(p.kernel, p.d, [&](auto K, auto D) {
+    constexpr int KERN = decltype(K)::value, DD = decltype(D)::value;
+    hipLaunchKernelGGL((hess_contract_kernel<KERN, DD>), dim3(DD, pc), dim3(256), 0, c->stream, p, c->Xt, c->xq_dev, ldz, c->invp,
+                       c->zvec, c->Wt, h1, h2);
+  });
+}
+
+// stage 1: derivative rows into Wt rows 1..d, 2: Gram of those rows after the forward sweep
+void gpg_launch_hess_stage(gpg_ctx* c, const AsmParams& p, int nxp, double* T, int stage) {
+  gpg_for_kern_d(p.kernel, p.d, [&](auto K, auto D) {
+    constexpr int KERN = decltype(K)::value, DD = decltype(D)::value;
+    if (stage == 1)
+      hipLaunchKernelGGL((cross_dx_rows_kernel<KERN, DD>), dim3((p.n + 255) / 256), dim3(256), 0, c->stream, p, c->Xt,
+                         c->xq_dev, nxp, c->invp, c->Wt);
+    else
+      hipLaunchKernelGGL((rows_gram_kernel<DD>), dim3(DD), dim3(256), 0, c->stream, c->Wt, nxp, c->Npad, T);
+  });
 }
 
 // ---- products with the factor in place (condition number) ------------------------------------
