@@ -210,12 +210,11 @@ int gpg_create(gpg_ctx** out, int device, int n_eval, int dim, int use_grad, int
   c->ld = c->Npad + c->R;
   c->nb_outer = c->Npad >= 8192 ? 512 : 256;   // wider panels amortise the C-tile traffic of the trailing update (measured)
   // factorisation schedule (measured, profiles/r01_tile_probe.log): one dataflow launch, 64-tile kernel for small
-  // matrices (shorter dependency chain), 128-tile kernel above; chol_impl 0 = blocked right-looking (A/B runs)
-  c->chol_impl = 1;
+  // matrices (shorter dependency chain), 128-tile kernel above
+  c->factor_mode = GPG_FACTOR_AUTO;
   if (const char* e = getenv("GPG_OVERLAP_INVERSE")) c->overlap_inverse = atoi(e);   // diagnostic override (A/B runs)
   if (const char* e = getenv("GPG_PAIR")) c->pair_mode = atoi(e);                    // diagnostic override (A/B runs)
   if (const char* e = getenv("GPG_ROWS_MAX_TASKS")) { const int v = atoi(e); if (v >= 64) c->rows_max_tasks = v; }   // diagnostic override
-  c->tail_cols = 12288;
 #define CREATE_OK(call)                                                              \
   do {                                                                               \
     hipError_t e_ = (call);                                                          \
@@ -469,7 +468,7 @@ static int gpg_lkd_grad_once(gpg_ctx* c, const gpg_hp* hp, gpg_lkd_out* out, dou
   // Large matrices: look at the factorisation's info before spending two more N^3/3 sweeps on a failed factor.  Small ones
   // (the sweeps cost less than a host round trip is worth): everything is enqueued at once and judged at the end; the kernels
   // run to completion on whatever a failed factorisation left behind (their waits depend on flags, not on values).
-  const bool one_sync = c->Npad <= 2048 || (overlap && c->Npad <= 12288);
+  const bool one_sync = c->Npad <= 2048 || (overlap && c->Npad <= GPG_AUTO_TILE64_MAX_COLS);
   if (!one_sync) {
     GPG_HIP_OK(c, hipStreamSynchronize(c->stream));
     GPG_HIP_OK(c, hipGetLastError());
@@ -520,8 +519,6 @@ static int gpg_lkd_grad_once(gpg_ctx* c, const gpg_hp* hp, gpg_lkd_out* out, dou
 // large ones (128-tile regime) do so at their two ends.  Workspaces are sized once for the largest batch the shape
 // will use, not for this call's m: a later, larger call must not pay a multi-GB reallocation.
 static int batch_plan(gpg_ctx* c, int m) {
-  const bool small = c->tail_cols > 0 && c->Npad <= c->tail_cols;
-  const bool large_df = !small && c->chol_impl == 1;
   int bmax = c->batch_max;
   if (bmax < 0) {
     if (c->Npad < 2048) {   // 64-tile kernel: enough matrices to put ~8k tiles in flight
@@ -543,7 +540,7 @@ static int batch_plan(gpg_ctx* c, int m) {
     if (bmax > 1) bmax = bmax < 8 ? 8 : (bmax > 128 ? 128 : bmax);
   }
   if (c->batch_max > 1 && c->Npad > 32768 && bmax > 3) bmax = 3;
-  if (!(small || large_df) || bmax <= 1 || m <= 1) return 1;
+  if (!gpg_factor_dataflow(c) || bmax <= 1 || m <= 1) return 1;   // the blocked schedule takes one matrix at a time
   const size_t bytesA = sizeof(double) * c->A_elems;
   int Bcap = bmax;
   while (Bcap > 1 && bytesA * Bcap > ((size_t)120 << 30)) --Bcap;  // at most 120 GB of extra workspaces (288 GB per GPU)
@@ -702,8 +699,7 @@ static int gpg_lkd_grad_batch_once(gpg_ctx* c, int m, const double* hp_rows, int
   const size_t nn = (size_t)c->Npad * c->Npad;
   if (B > 8) B = 8;
   while (B > 1 && 2 * nn * sizeof(double) * B > ((size_t)96 << 30)) --B;
-  const bool dataflow = c->chol_impl != 0 || c->tail_cols != 0;
-  if (!dataflow || c->Npad < 512) B = 1;           // blocked mode / tiny matrices: one row at a time through gpg_lkd_grad's steps
+  if (!gpg_factor_dataflow(c) || c->Npad < 512) B = 1;           // blocked mode / tiny matrices: one row at a time through gpg_lkd_grad's steps
   if (B > c->gbatch_cap) {
     if (c->batchW) (void)hipFree(c->batchW);
     if (c->batchM) (void)hipFree(c->batchM);
@@ -903,10 +899,9 @@ static int with_fallback(gpg_ctx* c, const std::function<int()>& f) {
     c->fail_kind = 0;
     rc = f();
   }
-  if (rc == -4 && c && (c->chol_impl != 0 || c->tail_cols != 0)) {
+  if (rc == -4 && c && gpg_factor_dataflow(c)) {
     drain_streams(c);
-    c->chol_impl = 0;
-    c->tail_cols = 0;
+    c->factor_mode = GPG_FACTOR_BLOCKED;
     c->factor_fallbacks += 1;
     rc = f();
   }
@@ -1494,13 +1489,11 @@ int gpg_prof_read(gpg_ctx* c, double ms[GPG_PROF_NCAT], long long count[GPG_PROF
 
 int gpg_set_factor_mode(gpg_ctx* c, int mode) {
   if (!c) return -1;
-  switch (mode) {
-    case GPG_FACTOR_AUTO:    c->chol_impl = 1; c->tail_cols = 12288; break;
-    case GPG_FACTOR_BLOCKED: c->chol_impl = 0; c->tail_cols = 0; break;
-    case GPG_FACTOR_TILE64:  c->chol_impl = 0; c->tail_cols = 1 << 30; break;
-    case GPG_FACTOR_TILE128: c->chol_impl = 1; c->tail_cols = 0; break;
-    default: c->err = "unknown factor mode"; return -1;
+  if (mode != GPG_FACTOR_AUTO && mode != GPG_FACTOR_BLOCKED && mode != GPG_FACTOR_TILE64 && mode != GPG_FACTOR_TILE128) {
+    c->err = "unknown factor mode";
+    return -1;
   }
+  c->factor_mode = (gpg_factor_mode)mode;
   c->solve_dataflow = 1;                                    // re-arm what a timed-out wait switched off (with_fallback)
   if (c->overlap_inverse == 0 && c->overlap_fallbacks > 0) c->overlap_inverse = 2;
   return 0;
@@ -1550,9 +1543,7 @@ int gpg_set_task_order(gpg_ctx* c, int order) {
 
 int gpg_set_lookahead(gpg_ctx* c, int on) {
   if (!c) return -1;
-  c->lookahead = (on & 1) ? 1 : 0;
-  c->gemm_impl = (on & 2) ? 0 : 1;   // bit 1: fall back to the register-staged 128x128 kernel (A/B runs)
-  c->panel_impl = (on & 4) ? 0 : 1;  // bit 2: fall back to per-64-column trsm + gemm launches for B_p (A/B runs)
+  c->lookahead = (on & 1) ? 1 : 0;   // bits 1 and 2 once selected kernel variants that are gone: accepted and ignored
   return 0;
 }
 

@@ -1,17 +1,20 @@
 // Cholesky entry point (gpg_cholesky) and the BLOCKED right-looking schedule for gfx950, fp64, column-major lower
 // triangle, in place.  Replaces scipy.linalg.cho_factor(Kcov_precon, lower=True) (reference Kernel.py:251; LAPACK
 // dpotrf).  The default schedule is the dataflow one of cholesky_dataflow.hip (one launch per factorisation); what
-// lives here is used by GPG_FACTOR_BLOCKED (A/B measurements, fallback when dataflow launches share a device) and by
-// the forward sweeps of the prediction / gradient paths.
+// lives here is used by GPG_FACTOR_BLOCKED (parity reference, fallback after a timed-out dataflow launch) and by the
+// blocked sweeps of the prediction / gradient paths (gpg_forward_rows, gpg_inverse_from_factor), which also run in the
+// default mode above rows_max_tasks and whenever a dataflow launch is refused.
 //
-// Blocked schedule: panel (width nb_outer) = 64-wide inner steps of
-//     potrf64   one wave, a matrix row per lane held in registers
-//     trsm64    X <- X L_kk^-T, four lanes per matrix row (rows are contiguous in column-major -> coalesced)
-//     gemm      update of the remaining panel columns        (B_p as one fused launch: panel_solve_kernel)
-// followed by the trailing update  C -= A_panel A_panel^T  on v_mfma_f64_16x16x4_f64
-// (64 cycles / instruction / SIMD measured = 78.6 TFLOP/s chip peak), 128x128 tiles, LDS-DMA ring or direct
-// fragment loads, the C tile loaded straight into the accumulators.
-// Right-hand-side rows stored below the matrix (rows Npad .. ld) ride along every trsm / gemm, which
+// Blocked schedule, one kernel per step.  Per panel (width nb_outer, a short last one):
+//     diagonal block   64-wide inner steps of
+//         potrf64_kernel                one wave, a matrix row per lane held in registers
+//         trsm64_kernel                 X <- X L_kk^-T, four lanes per matrix row (rows are contiguous in column-major -> coalesced)
+//         gemm_nt_minus_kernel<64,64>   update of the rest of the diagonal block (lower tiles)
+//     rows below       panel_solve_kernel: the whole panel's substitution in one fused launch
+//     trailing update  gemm_dma_kernel<4>: C -= A_panel A_panel^T on v_mfma_f64_16x16x4_f64 (64 cycles / instruction / SIMD
+//                      measured = 78.6 TFLOP/s chip peak), 128x128 tiles from a live-tile list, the panel streamed through an
+//                      LDS-DMA ring, the C tile loaded straight into the accumulators
+// Right-hand-side rows stored below the matrix (rows Npad .. ld) ride along every solve / update, which
 // yields L^-1 B for free (no separate forward substitution on the likelihood path).
 #include "chol_device.h"
 
@@ -72,18 +75,41 @@ panel_solve_kernel(const double* __restrict__ L, int ldl, const double* __restri
 }
 
 // ------------------------------------------------------------------------------------------------
-// gemm_nt_minus<BM, BN>:  C[M x Nc] -= A[M x K] * B[Nc x K]^T   (all column-major)
-//   M multiple of 64, Nc multiple of BN, K multiple of 8.  lower != 0: C's origin lies on the matrix
-//   diagonal and tiles entirely above it are skipped; tiles with m0 < skipM and n0 < skipN are skipped too.
-// 4 waves as 2 x 2; each wave owns (BM/2) x (BN/2) of C as 16x16 MFMA blocks.  The MFMA "A" operand
-// is fed from the C-column side and the "B" operand from the C-row side, so that lane&15 indexes C's
+// The C tile of one wave in the MFMA accumulator layout shared by the two update kernels below: block (ni, mi), element r
+// of lane (l15, l4) is C[mi 16 + l15, ni 16 + 4 r + l4] relative to the wave's corner (Cw points at the lane's (l15, l4)).
+// The MFMA "A" operand is fed from the C-column side and the "B" operand from the C-row side, so that lane&15 indexes C's
 // row: every accumulator load/store instruction touches 4 columns x 128 contiguous bytes.
+// ------------------------------------------------------------------------------------------------
+template <int NI, int MI>
+__device__ __forceinline__ void acc_load(d4 (&acc)[NI][MI], const double* Cw, int ldc) {
+#pragma unroll
+  for (int ni = 0; ni < NI; ++ni)
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc[ni][mi][r] = Cw[mi * 16 + (size_t)(ni * 16 + 4 * r) * ldc];
+}
+template <int NI, int MI>
+__device__ __forceinline__ void acc_store(const d4 (&acc)[NI][MI], double* Cw, int ldc) {
+#pragma unroll
+  for (int ni = 0; ni < NI; ++ni)
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) Cw[mi * 16 + (size_t)(ni * 16 + 4 * r) * ldc] = acc[ni][mi][r];
+}
+
+// ------------------------------------------------------------------------------------------------
+// gemm_nt_minus<BM, BN>:  C[M x Nc] -= A[M x K] * B[Nc x K]^T   (all column-major), register-staged through LDS.
+//   M multiple of 64, Nc multiple of BN, K multiple of 8.  lower != 0: C's origin lies on the matrix
+//   diagonal and tiles entirely above it are skipped.  Instantiated as <64, 64> with lower = 1 only: the update of
+//   a diagonal block (a few tiles; the 128 x 128 updates all go to gemm_dma_kernel).
+// 4 waves as 2 x 2; each wave owns (BM/2) x (BN/2) of C as 16x16 MFMA blocks.
 // ------------------------------------------------------------------------------------------------
 template <int BM, int BN>
 __global__ void __launch_bounds__(256, 2)
 gemm_nt_minus_kernel(double* __restrict__ C, int ldc, const double* __restrict__ A, int lda,
-                     const double* __restrict__ B, int ldb, int M, int Nc, int K, int lower, int skipM, int skipN,
-                     const int* __restrict__ tilemap, int ntiles) {
+                     const double* __restrict__ B, int ldb, int M, int Nc, int K, int lower) {
   constexpr int KB = 8;
   constexpr int SA = BM + 16, SB = BN + 16;   // row strides: +128 B keeps ds_read_b64 conflict-free
   constexpr int MI = BM / 32, NI = BN / 32;   // 16x16 blocks per wave
@@ -91,40 +117,18 @@ gemm_nt_minus_kernel(double* __restrict__ C, int ldc, const double* __restrict__
   __shared__ __attribute__((aligned(16))) double sA[2][KB][SA];
   __shared__ __attribute__((aligned(16))) double sB[2][KB][SB];
 
-  int m0, n0;
-  if (tilemap) {
-    // 1-D grid over a precomputed list of live tiles in super-tile-major order.  Workgroups b and b + 8
-    // share an XCD (round-robin dispatch), so each XCD is handed one contiguous chunk of the list: the
-    // tiles resident on an XCD at any time share panel slices, which then hit in that XCD's L2.
-    const int nwg = ntiles, b = blockIdx.x;
-    const int xcd = b & 7, q = nwg >> 3, r = nwg & 7;
-    const int v = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-    const int t = tilemap[v];
-    m0 = (t & 0xffff) * BM;
-    n0 = (t >> 16) * BN;
-  } else {
-    m0 = blockIdx.x * BM;
-    n0 = blockIdx.y * BN;
-    if (lower && m0 + BM <= n0) return;
-    if (m0 < skipM && n0 < skipN) return;   // region owned by the look-ahead stream
-  }
+  const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
+  if (lower && m0 + BM <= n0) return;
 
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int wm = w & 1, wn = w >> 1;
   const int l15 = lane & 15, l4 = lane >> 4;
-  const bool wave_active = (m0 + wm * (BM / 2)) < M;   // ragged last row tile (M % 128 == 64)
+  const bool wave_active = (m0 + wm * (BM / 2)) < M;   // ragged last row tile
 
   // ---- accumulators start as the C tile ----------------------------------------------------------
   d4 acc[NI][MI] = {};
   double* Cw = C + (size_t)(m0 + wm * (BM / 2) + l15) + (size_t)(n0 + wn * (BN / 2) + l4) * ldc;
-  if (wave_active) {
-#pragma unroll
-    for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc[ni][mi][r] = Cw[mi * 16 + (size_t)(ni * 16 + 4 * r) * ldc];
-  }
+  if (wave_active) acc_load(acc, Cw, ldc);
 
   // ---- global -> register -> LDS staging of one k-chunk (per-thread constants hoisted) ------------------
   // thread -> (row pair p, k) of the chunk; LA / LB double2 loads per thread per chunk
@@ -188,34 +192,27 @@ gemm_nt_minus_kernel(double* __restrict__ C, int ldc, const double* __restrict__
 #undef GPG_SSTORE
 #undef GPG_COMPUTE
 
-  if (wave_active) {
-#pragma unroll
-    for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) Cw[mi * 16 + (size_t)(ni * 16 + 4 * r) * ldc] = acc[ni][mi][r];
-  }
+  if (wave_active) acc_store(acc, Cw, ldc);
 }
 
 // ------------------------------------------------------------------------------------------------
 // gemm_dma_kernel: the 128 x 128 tile update  C -= A B^T  with the panel streamed by LDS-DMA.
-// Same tile / wave / MFMA mapping as gemm_nt_minus_kernel<128,128>, but the k-chunks (8 deep) are
-// written straight into a 4-stage LDS ring with global_load_lds_dwordx4: one wave-instruction moves one
+// Tile / wave / MFMA mapping of gemm_nt_minus_kernel with 128 x 128 tiles (a wave owns 64 x 64), but the k-chunks
+// (8 deep) are written straight into a 4-stage LDS ring with global_load_lds_dwordx4: one wave-instruction moves one
 // 1 KiB k-row of the A or B slice (rows are contiguous in the column-major panel and padded by 128 B in
 // LDS, so each row is exactly one lane-linear DMA).  Three chunks stay in flight across the single raw
 // s_barrier per chunk (counted vmcnt, never __syncthreads(), which would drain the DMAs); no staging
 // VGPRs, no ds_write.  The sign of the update is folded into the A fragment (one v_xor per fragment).
+// tilemap != nullptr: 1-D grid over a list of live tiles (launch_gemm_trailing: lower trapezoid, minus the look-ahead
+// block); else a 2-D grid over every tile of C (the row sweeps).
 // ------------------------------------------------------------------------------------------------
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef const __attribute__((address_space(1))) void* glb_ptr_t;
 
-
 template <int S>
 __global__ void __launch_bounds__(256, 2)
 gemm_dma_kernel(double* __restrict__ C, int ldc, const double* __restrict__ A, int lda, const double* __restrict__ B,
-                int ldb, int M, int Nc, int K, int lower, int skipM, int skipN, const int* __restrict__ tilemap,
-                int ntiles) {
+                int ldb, int M, int Nc, int K, const int* __restrict__ tilemap, int ntiles) {
   constexpr int BM = 128, BN = 128, KB = 8;
   constexpr int ROW = 144;                 // doubles per LDS k-row (128 + 16 pad: conflict-free ds_read_b64)
   constexpr int STAGE = 2 * KB * ROW;      // A rows then B rows
@@ -223,6 +220,9 @@ gemm_dma_kernel(double* __restrict__ C, int ldc, const double* __restrict__ A, i
 
   int m0, n0;
   if (tilemap) {
+    // The list is in super-tile-major order.  Workgroups b and b + 8 share an XCD (round-robin dispatch), so each XCD
+    // is handed one contiguous chunk of the list: the tiles resident on an XCD at any time share panel slices, which
+    // then hit in that XCD's L2.
     const int nwg = ntiles, b = blockIdx.x;
     const int xcd = b & 7, q = nwg >> 3, r = nwg & 7;
     const int v = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
@@ -232,8 +232,6 @@ gemm_dma_kernel(double* __restrict__ C, int ldc, const double* __restrict__ A, i
   } else {
     m0 = blockIdx.x * BM;
     n0 = blockIdx.y * BN;
-    if (lower && m0 + BM <= n0) return;
-    if (m0 < skipM && n0 < skipN) return;
   }
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int wm = w & 1, wn = w >> 1;
@@ -245,14 +243,7 @@ gemm_dma_kernel(double* __restrict__ C, int ldc, const double* __restrict__ A, i
 #endif
   d4 acc[4][4] = {};
   double* Cw = C + (size_t)(m0 + wm * 64 + l15) + (size_t)(n0 + wn * 64 + l4) * ldc;
-  if (wave_active) {
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc[ni][mi][r] = Cw[mi * 16 + (size_t)(ni * 16 + 4 * r) * ldc];
-  }
+  if (wave_active) acc_load(acc, Cw, ldc);
 
   // per-lane DMA sources: this wave moves k-rows w and w + 4 of every chunk, for A and for B
   int rowa = m0 + 2 * lane;
@@ -339,14 +330,7 @@ gemm_dma_kernel(double* __restrict__ C, int ldc, const double* __restrict__ A, i
 #undef GPG_DMA_COMPUTE
 #undef GPG_WAIT_STEADY
 
-  if (wave_active) {
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) Cw[mi * 16 + (size_t)(ni * 16 + 4 * r) * ldc] = acc[ni][mi][r];
-  }
+  if (wave_active) acc_store(acc, Cw, ldc);
 #ifdef GPG_STAMP
   // timeline record of wave 0 (diagnostic): hw id, start, main-loop start, main-loop end, stores issued
   if (lane == 0 && w == 0 && blockIdx.x < 4096 && g_stamp_buf != nullptr) {
@@ -360,110 +344,17 @@ gemm_dma_kernel(double* __restrict__ C, int ldc, const double* __restrict__ A, i
 #endif
 }
 
-// ------------------------------------------------------------------------------------------------
-// gemm_direct_kernel: 128 x 128 tile update C -= A B^T with NO LDS: every wave loads its MFMA operand
-// fragments straight from global memory in fragment layout (lane&15 -> row of the slice: 128 contiguous
-// bytes; lane>>4 -> k: four segments per instruction), PF k-steps ahead in registers.  The two waves that
-// share a row slice hit in the vector L1.  No DMA issue stalls, no barriers: waves run independently.
-// ------------------------------------------------------------------------------------------------
-template <int PF>
-__global__ void __launch_bounds__(256, 2)
-gemm_direct_kernel(double* __restrict__ C, int ldc, const double* __restrict__ A, int lda, const double* __restrict__ B,
-                   int ldb, int M, int Nc, int K, int lower, int skipM, int skipN, const int* __restrict__ tilemap,
-                   int ntiles) {
-  constexpr int BM = 128, BN = 128;
-  int m0, n0;
-  if (tilemap) {
-    const int nwg = ntiles, b = blockIdx.x;
-    const int xcd = b & 7, q = nwg >> 3, r = nwg & 7;
-    const int v = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-    const int t = tilemap[v];
-    m0 = (t & 0xffff) * BM;
-    n0 = (t >> 16) * BN;
-  } else {
-    m0 = blockIdx.x * BM;
-    n0 = blockIdx.y * BN;
-    if (lower && m0 + BM <= n0) return;
-    if (m0 < skipM && n0 < skipN) return;
-  }
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int wm = w & 1, wn = w >> 1;
-  const int l15 = lane & 15, l4 = lane >> 4;
-  const bool wave_active = (m0 + wm * 64) < M;
-
-  d4 acc[4][4];
-  double* Cw = C + (size_t)(m0 + wm * 64 + l15) + (size_t)(n0 + wn * 64 + l4) * ldc;
-  if (wave_active) {
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc[ni][mi][r] = Cw[mi * 16 + (size_t)(ni * 16 + 4 * r) * ldc];
-  } else {
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi) acc[ni][mi] = d4{0, 0, 0, 0};
-  }
-  int rowa = m0 + wm * 64 + l15;
-  rowa = wave_active ? rowa : m0 + l15;                    // inactive wave of a ragged tile: recompute valid rows, never store
-  const double* pa = A + rowa + (size_t)l4 * lda;
-  const double* pb = B + n0 + wn * 64 + l15 + (size_t)l4 * ldb;
-  const size_t sa = (size_t)4 * lda, sb = (size_t)4 * ldb;
-
-  double f[PF + 1][8];
-#define GPG_DR_LOAD(set)                                                              \
-  {                                                                                   \
-    _Pragma("unroll") for (int mi = 0; mi < 4; ++mi) f[set][mi] = pa[mi * 16];         \
-    _Pragma("unroll") for (int ni = 0; ni < 4; ++ni) f[set][4 + ni] = pb[ni * 16];     \
-    pa += sa;                                                                         \
-    pb += sb;                                                                         \
-  }
-#define GPG_DR_MFMA(set)                                                              \
-  {                                                                                   \
-    double fm[4];                                                                     \
-    _Pragma("unroll") for (int mi = 0; mi < 4; ++mi) fm[mi] = -f[set][mi];             \
-    _Pragma("unroll") for (int ni = 0; ni < 4; ++ni)                                   \
-      _Pragma("unroll") for (int mi = 0; mi < 4; ++mi)                                 \
-        acc[ni][mi] = __builtin_amdgcn_mfma_f64_16x16x4f64(f[set][4 + ni], fm[mi], acc[ni][mi], 0, 0, 0); \
-  }
-  const int nstep = K / 4;   // K is a multiple of 4 (PF + 1): the ring index stays static under the unroll
-#pragma unroll
-  for (int s = 0; s < PF; ++s) GPG_DR_LOAD(s)
-  for (int s0 = 0; s0 < nstep; s0 += PF + 1) {
-#pragma unroll
-    for (int u = 0; u <= PF; ++u) {
-      if (s0 + u + PF < nstep) GPG_DR_LOAD((u + PF) % (PF + 1))
-      __builtin_amdgcn_sched_barrier(0);
-      GPG_DR_MFMA(u)
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-#undef GPG_DR_LOAD
-#undef GPG_DR_MFMA
-  if (wave_active) {
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) Cw[mi * 16 + (size_t)(ni * 16 + 4 * r) * ldc] = acc[ni][mi][r];
-  }
-}
-
+// C[M x Nc] -= A B^T over a plain grid of tiles.  <128, 128>: every tile of C (the row sweeps), gemm_dma_kernel;
+// <64, 64>: C is a diagonal block, lower tiles only, gemm_nt_minus_kernel.
 template <int BM, int BN>
-void launch_gemm(gpg_ctx* c, double* C, int ldc, const double* A, int lda, const double* B, int ldb, int M, int Nc,
-                 int K, int lower, int skipM = 0, int skipN = 0) {
+void launch_gemm(gpg_ctx* c, double* C, int ldc, const double* A, int lda, const double* B, int ldb, int M, int Nc, int K) {
+  static_assert((BM == 128 && BN == 128) || (BM == 64 && BN == 64), "one kernel per step: 128 x 128 or the 64 x 64 diagonal update");
   if (M <= 0 || Nc <= 0 || K <= 0) return;
   dim3 grid((M + BM - 1) / BM, Nc / BN);
-  if (BM == 128 && BN == 128 && c->gemm_impl == 1) {
-    hipLaunchKernelGGL(gemm_dma_kernel<4>, grid, dim3(256), 0, c->stream, C, ldc, A, lda, B, ldb, M, Nc, K, lower, skipM,
-                       skipN, (const int*)nullptr, 0);
-    return;
-  }
-  hipLaunchKernelGGL((gemm_nt_minus_kernel<BM, BN>), grid, dim3(256), 0, c->stream, C, ldc, A, lda, B, ldb, M, Nc, K,
-                     lower, skipM, skipN, (const int*)nullptr, 0);
+  if constexpr (BM == 128)
+    hipLaunchKernelGGL(gemm_dma_kernel<4>, grid, dim3(256), 0, c->stream, C, ldc, A, lda, B, ldb, M, Nc, K, (const int*)nullptr, 0);
+  else
+    hipLaunchKernelGGL((gemm_nt_minus_kernel<64, 64>), grid, dim3(256), 0, c->stream, C, ldc, A, lda, B, ldb, M, Nc, K, 1);
 }
 
 // Live-tile list of a lower-trapezoid update (Mt x Nt tiles of 128, tiles above the diagonal and the
@@ -501,33 +392,13 @@ void launch_gemm_trailing(gpg_ctx* c, double* C, int ldc, const double* A, int l
                           int Nc, int K, int skip) {
   const TileMap& tm = get_tilemap(c, (M + 127) / 128, Nc / 128, skip / 128);
   if (tm.n <= 0) return;
-  if (c->gemm_impl == 1) {
-    hipLaunchKernelGGL(gemm_dma_kernel<4>, dim3(tm.n), dim3(256), 0, c->stream, C, ldc, A, lda, B, ldb, M, Nc, K, 1, 0, 0,
-                       (const int*)tm.dev, tm.n);
-    return;
-  }
-  if (c->gemm_impl == 3) {
-    hipLaunchKernelGGL(gemm_direct_kernel<3>, dim3(tm.n), dim3(256), 0, c->stream, C, ldc, A, lda, B, ldb, M, Nc, K, 1, 0, 0,
-                       (const int*)tm.dev, tm.n);
-    return;
-  }
-  hipLaunchKernelGGL((gemm_nt_minus_kernel<128, 128>), dim3(tm.n), dim3(256), 0, c->stream, C, ldc, A, lda, B, ldb, M, Nc,
-                     K, 1, 0, 0, (const int*)tm.dev, tm.n);
+  hipLaunchKernelGGL(gemm_dma_kernel<4>, dim3(tm.n), dim3(256), 0, c->stream, C, ldc, A, lda, B, ldb, M, Nc, K,
+                     (const int*)tm.dev, tm.n);
 }
 
 }  // namespace
 
-// Factorise the Npad x Npad matrix held in c->A; rows [Npad, ld) are right-hand-side rows.
-//
-// Per panel p (columns [k0, k1), width nb_outer):
-//   D_p  factor the nb x nb diagonal block               (potrf64 + small trsm/gemm; latency-bound, tiny)
-//   B_p  solve the rows below it: 64-column trsm sweeps + MFMA updates inside the panel
-//   U_p  trailing update C -= A_panel A_panel^T on fp64 MFMA
-// Look-ahead: D_(p+1) only needs the next diagonal block updated, so a second (high-priority) stream
-// applies panel p to that block and factors it while the main stream runs the big U_p (which skips
-// that block).  The serial pivot chain of potrf is thereby hidden behind the trailing update.
-//   main stream : [wait D_p] B_p, U_p (minus next diag block), [wait D_(p+1)] B_(p+1), ...
-//   diag stream : [wait B_p] update next diag block with panel p, D_(p+1)
+// D_p: factor the diagonal block [k0, k1) in 64-wide steps (potrf64, trsm64 of the block's rows below, 64 x 64 update)
 static void factor_diag_block(gpg_ctx* c, int k0, int k1) {
   const int ld = c->ld;
   double* A = c->A;
@@ -542,7 +413,7 @@ static void factor_diag_block(gpg_ctx* c, int k0, int k1) {
       hipLaunchKernelGGL(trsm64_kernel, dim3((rows + 63) / 64), dim3(256), 0, c->stream, A + (size_t)j0 + (size_t)j0 * ld,
                          ld, c->dinv + j0, A + (size_t)j1 + (size_t)j0 * ld, ld, rows);
       launch_gemm<64, 64>(c, A + (size_t)j1 + (size_t)j1 * ld, ld, A + (size_t)j1 + (size_t)j0 * ld, ld,
-                          A + (size_t)j1 + (size_t)j0 * ld, ld, rows, rows, GPG_NBI, 1);
+                          A + (size_t)j1 + (size_t)j0 * ld, ld, rows, rows, GPG_NBI);
       gpg_prof_end(c);
     }
   }
@@ -554,49 +425,44 @@ static void launch_panel_solve(gpg_ctx* c, const double* Lpp, int ldl, const dou
   hipLaunchKernelGGL(panel_solve_kernel, dim3((rows + 63) / 64), dim3(256), 0, c->stream, Lpp, ldl, dinv, X, ldx, rows, nb);
 }
 
+// B_p: solve the rows below the diagonal block [k0, k1), right-hand-side rows included, in one fused launch
 static void solve_below_block(gpg_ctx* c, int k0, int k1) {
   const int ld = c->ld;
   double* A = c->A;
   const int rows = ld - k1;
   if (rows <= 0) return;
-  if (c->panel_impl == 1) {   // one fused launch per panel
-    gpg_prof_begin(c, GPG_PROF_TRSM, (double)rows * (double)(k1 - k0) * (double)(k1 - k0));
-    launch_panel_solve(c, A + (size_t)k0 + (size_t)k0 * ld, ld, c->dinv + k0, A + (size_t)k1 + (size_t)k0 * ld, ld, rows,
-                       k1 - k0);
-    gpg_prof_end(c);
-    return;
-  }
-  for (int j0 = k0; j0 < k1; j0 += GPG_NBI) {
-    const int j1 = j0 + GPG_NBI;
-    gpg_prof_begin(c, GPG_PROF_TRSM, (double)rows * 64.0 * 64.0);
-    hipLaunchKernelGGL(trsm64_kernel, dim3((rows + 63) / 64), dim3(256), 0, c->stream, A + (size_t)j0 + (size_t)j0 * ld, ld,
-                       c->dinv + j0, A + (size_t)k1 + (size_t)j0 * ld, ld, rows);
-    gpg_prof_end(c);
-    const int ncols = k1 - j1;
-    if (ncols > 0) {   // X[:, j1:k1] -= X[:, j0:j1] L[j1:k1, j0:j1]^T
-      gpg_prof_begin(c, GPG_PROF_GEMM_PANEL, 2.0 * (double)rows * ncols * 64.0);
-      launch_gemm<128, 64>(c, A + (size_t)k1 + (size_t)j1 * ld, ld, A + (size_t)k1 + (size_t)j0 * ld, ld,
-                           A + (size_t)j1 + (size_t)j0 * ld, ld, rows, ncols, GPG_NBI, 0);
-      gpg_prof_end(c);
-    }
-  }
+  gpg_prof_begin(c, GPG_PROF_TRSM, (double)rows * (double)(k1 - k0) * (double)(k1 - k0));
+  launch_panel_solve(c, A + (size_t)k0 + (size_t)k0 * ld, ld, c->dinv + k0, A + (size_t)k1 + (size_t)k0 * ld, ld, rows,
+                     k1 - k0);
+  gpg_prof_end(c);
 }
 
+// Factorise the Npad x Npad matrix held in c->A; rows [Npad, ld) are right-hand-side rows.  The dataflow modes hand
+// the whole matrix to one launch of cholesky_dataflow.hip; what follows is the blocked schedule.
+//
+// Per panel p (columns [k0, k1), width nb_outer, the last one shorter):
+//   D_p  factor the diagonal block                        (factor_diag_block; latency-bound, tiny)
+//   B_p  solve the rows below it                          (solve_below_block)
+//   U_p  trailing update C -= A_panel A_panel^T           (launch_gemm_trailing)
+// Look-ahead: D_(p+1) only needs the next diagonal block updated, so a second (high-priority) stream
+// applies panel p to that block and factors it while the main stream runs the big U_p (whose tile list
+// leaves that block out).  The serial pivot chain of potrf is thereby hidden behind the trailing update.
+//   main stream : [wait D_p] B_p, U_p (minus next diag block), [wait D_(p+1)] B_(p+1), ...
+//   diag stream : [wait B_p] update next diag block with panel p, D_(p+1)
 void gpg_cholesky(gpg_ctx* c) {
-  const int ld = c->ld, Npad = c->Npad;
+  const int ld = c->ld, Npad = c->Npad, NB = c->nb_outer;
+  if (gpg_single_uses_tile64(c)) {   // small matrix: shorter dependency chain on 64-tiles
+    gpg_launch_tile_chol(c);
+    return;
+  }
+  if (gpg_single_uses_tile128(c)) {
+    gpg_launch_tile128_chol(c);
+    return;
+  }
   double* A = c->A;
   hipStream_t sM = c->stream, sD = c->lookahead ? c->stream_upd : c->stream;
   const bool two = (sD != sM);
-  // panel boundaries: wide panels (nb_big) while at least big_rows columns remain -- the trailing update then
-  // streams the C tiles half as often -- and nb_outer afterwards, where the serial diagonal chain matters more
-  std::vector<int> kb;
-  for (int k = 0; k < Npad;) {
-    kb.push_back(k);
-    const int nbw = (c->nb_big > c->nb_outer && Npad - k >= c->big_rows) ? c->nb_big : c->nb_outer;
-    k = (k + nbw < Npad) ? k + nbw : Npad;
-  }
-  kb.push_back(Npad);
-  const int npanel = (int)kb.size() - 1;
+  const int npanel = (Npad + NB - 1) / NB;
   while ((int)c->ev_panel.size() < npanel + 1) {
     hipEvent_t e1, e2;
     (void)hipEventCreateWithFlags(&e1, hipEventDisableTiming);
@@ -604,35 +470,16 @@ void gpg_cholesky(gpg_ctx* c) {
     c->ev_panel.push_back(e1);   // ev_panel[p]: diagonal block p factorised (diag stream)
     c->ev_upd.push_back(e2);     // ev_upd[p]  : rows below panel p solved (main stream)
   }
-  // D_0 follows the assembly on the main stream
-  c->stream = sM;
-  if (c->tail_cols > 0 && Npad <= c->tail_cols) {   // small matrix: the dataflow kernel does all of it
-    gpg_launch_tile_chol(c, 0);
-    return;
-  }
-  if (c->chol_impl == 1) {
-    gpg_launch_tile128_chol(c);
-    return;
-  }
   c->last_factor_kernel = 0; c->last_factor_batch = 1;
-  factor_diag_block(c, 0, kb[1]);
+  // D_0 follows the assembly on the main stream
+  factor_diag_block(c, 0, NB < Npad ? NB : Npad);
   for (int p = 0; p < npanel; ++p) {
-    const int k0 = kb[p], k1 = kb[p + 1];                           // panel p = columns [k0, k1)
+    const int k0 = p * NB, k1 = (k0 + NB < Npad) ? k0 + NB : Npad;  // panel p = columns [k0, k1)
     c->stream = sM;
     if (two && p > 0) (void)hipStreamWaitEvent(sM, c->ev_panel[p], 0);
     solve_below_block(c, k0, k1);                                   // B_p (also carries the RHS rows)
     if (k1 >= Npad) break;
-    if (c->tail_cols > 0 && Npad - k1 <= c->tail_cols) {
-      // the rest is latency-bound: apply panel p to all of it, then hand over to the dataflow kernel
-      const double nt = (double)(Npad - k1);
-      gpg_prof_begin(c, GPG_PROF_GEMM_TRAIL, nt * (nt + 1.0) * (double)(k1 - k0));
-      launch_gemm_trailing(c, A + (size_t)k1 + (size_t)k1 * ld, ld, A + (size_t)k0 * ld + k1, ld, A + (size_t)k0 * ld + k1, ld,
-                           ld - k1, Npad - k1, k1 - k0, 0);
-      gpg_prof_end(c);
-      gpg_launch_tile_chol(c, k1);
-      break;
-    }
-    const int k2 = kb[p + 2];                                       // next diagonal block = [k1, k2)
+    const int k2 = (k1 + NB < Npad) ? k1 + NB : Npad;               // next diagonal block = [k1, k2)
     const int K = k1 - k0;
     const double* Ap = A + (size_t)k0 * ld;
     const double w = (double)(k2 - k1), nt = (double)(Npad - k1);
@@ -644,7 +491,7 @@ void gpg_cholesky(gpg_ctx* c) {
       c->stream = sD;
       (void)hipStreamWaitEvent(sD, c->ev_upd[p], 0);
       gpg_prof_begin(c, GPG_PROF_POTRF, flops_diag);
-      launch_gemm<64, 64>(c, A + (size_t)k1 + (size_t)k1 * ld, ld, Ap + k1, ld, Ap + k1, ld, k2 - k1, k2 - k1, K, 1);
+      launch_gemm<64, 64>(c, A + (size_t)k1 + (size_t)k1 * ld, ld, Ap + k1, ld, Ap + k1, ld, k2 - k1, k2 - k1, K);
       gpg_prof_end(c);
       factor_diag_block(c, k1, k2);
       (void)hipEventRecord(c->ev_panel[p + 1], sD);
@@ -672,22 +519,10 @@ void gpg_forward_rows(gpg_ctx* c, double* W, int ldw, int rows, int valid) {
   for (int k0 = 0; k0 < Npad; k0 += NB) {
     const int nbw = (Npad - k0) < NB ? (Npad - k0) : NB;
     const int k1 = k0 + nbw;
-    if (c->panel_impl == 1) {
-      launch_panel_solve(c, A + (size_t)k0 + (size_t)k0 * ld, ld, c->dinv + k0, W + (size_t)k0 * ldw, ldw, rows, nbw);
-    } else {
-      for (int j0 = k0; j0 < k1; j0 += GPG_NBI) {
-        const int j1 = j0 + GPG_NBI;
-        hipLaunchKernelGGL(trsm64_kernel, dim3((rows + 63) / 64), dim3(256), 0, c->stream,
-                           A + (size_t)j0 + (size_t)j0 * ld, ld, c->dinv + j0, W + (size_t)j0 * ldw, ldw, rows);
-        const int ncols = k1 - j1;
-        if (ncols > 0)
-          launch_gemm<128, 64>(c, W + (size_t)j1 * ldw, ldw, W + (size_t)j0 * ldw, ldw,
-                               A + (size_t)j1 + (size_t)j0 * ld, ld, rows, ncols, GPG_NBI, 0);
-      }
-    }
+    launch_panel_solve(c, A + (size_t)k0 + (size_t)k0 * ld, ld, c->dinv + k0, W + (size_t)k0 * ldw, ldw, rows, nbw);
     if (k1 < Npad)
       launch_gemm<128, 128>(c, W + (size_t)k1 * ldw, ldw, W + (size_t)k0 * ldw, ldw, A + (size_t)k1 + (size_t)k0 * ld,
-                            ld, rows, Npad - k1, nbw, 0);
+                            ld, rows, Npad - k1, nbw);
   }
 }
 
@@ -700,8 +535,8 @@ void gpg_forward_rows(gpg_ctx* c, double* W, int ldw, int rows, int valid) {
 // Minv == nullptr: step (1) only (gpg_loo needs W and no more than the point-diagonal blocks of W W^T).
 void gpg_inverse_from_factor(gpg_ctx* c, double* W, double* Minv) {
   // dataflow schedule: W = L^-T and Minv = -W W^T as one launch each (128 x 128 tiles); the blocked sweeps below remain
-  // for the blocked factor mode (A/B runs, fallback after a timed-out wait)
-  if (c->chol_impl != 0 || c->tail_cols != 0) {
+  // for the blocked factor mode (parity reference, fallback after a timed-out wait) and for a refused dataflow launch
+  if (gpg_factor_dataflow(c)) {
     if (Minv ? gpg_launch_tile128_inverse(c, W, Minv) : gpg_launch_tile128_trinv(c, W)) return;
   }
   const int ld = c->ld, Npad = c->Npad, NB = c->nb_outer, ldw = c->Npad;
@@ -710,22 +545,11 @@ void gpg_inverse_from_factor(gpg_ctx* c, double* W, double* Minv) {
   if (Minv) (void)hipMemsetAsync(Minv, 0, sizeof(double) * (size_t)ldw * Npad, c->stream);
   for (int k0 = 0; k0 < Npad; k0 += NB) {
     const int k1 = (k0 + NB < Npad) ? k0 + NB : Npad;
-    if (c->panel_impl == 1) {   // rows [j1, k1) of a column block are still zero when it is solved: harmless extra rows
-      launch_panel_solve(c, A + (size_t)k0 + (size_t)k0 * ld, ld, c->dinv + k0, W + (size_t)k0 * ldw, ldw, k1, k1 - k0);
-    } else {
-      for (int j0 = k0; j0 < k1; j0 += GPG_NBI) {
-        const int j1 = j0 + GPG_NBI;
-        hipLaunchKernelGGL(trsm64_kernel, dim3(j1 / 64), dim3(256), 0, c->stream, A + (size_t)j0 + (size_t)j0 * ld, ld,
-                           c->dinv + j0, W + (size_t)j0 * ldw, ldw, j1);
-        const int ncols = k1 - j1;
-        if (ncols > 0)
-          launch_gemm<128, 64>(c, W + (size_t)j1 * ldw, ldw, W + (size_t)j0 * ldw, ldw, A + (size_t)j1 + (size_t)j0 * ld, ld,
-                               j1, ncols, GPG_NBI, 0);
-      }
-    }
+    // rows below a 64-column step's own diagonal are still zero when it is solved: harmless extra rows
+    launch_panel_solve(c, A + (size_t)k0 + (size_t)k0 * ld, ld, c->dinv + k0, W + (size_t)k0 * ldw, ldw, k1, k1 - k0);
     if (k1 < Npad)
       launch_gemm<128, 128>(c, W + (size_t)k1 * ldw, ldw, W + (size_t)k0 * ldw, ldw, A + (size_t)k1 + (size_t)k0 * ld, ld,
-                            k1, Npad - k1, k1 - k0, 0);
+                            k1, Npad - k1, k1 - k0);
     if (Minv) launch_gemm_trailing(c, Minv, ldw, W + (size_t)k0 * ldw, ldw, W + (size_t)k0 * ldw, ldw, k1, k1, k1 - k0, 0);
   }
 }

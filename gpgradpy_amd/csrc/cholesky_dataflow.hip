@@ -183,17 +183,16 @@ static bool pair128_wanted(const gpg_ctx* c, int B) {
 //    at the same time and the chip is filled by problems whose single factorisation is latency-bound; the order per matrix is unchanged
 //    (progress argument holds).  The kernel gets the matrix of every task (batch_of) and the strides, also for B == 1.
 //  * not batched: one matrix, batch_of == nullptr and all strides 0 (the kernels branch on batch_of), task list without matrix indices.
-//    Only this form takes c0 > 0: the factorisation of the trailing block A[c0:, c0:] behind the blocked schedule (64-tiles).
 // The two forms stay apart for these kernel arguments only; the flag layout differs by tile size: per matrix the tile flags, the abort
 // word (that of matrix 0 serves the whole launch) and per diagonal tile four piece flags (64-tiles) or nine (128-tiles: 4 + 4 pieces and
 // the L21 flag), then the eight ticket words of the launch.  The overlapped inverse reads these flags from another stream.
 struct CholLaunch {
-  int tile, c0, B;
+  int tile, B;
   bool batched;
   double* A; size_t a_stride; double* dinv; int d_stride; int* info;
 };
 static void launch_chol_dataflow(gpg_ctx* c, const CholLaunch& L) {
-  const int B = L.B, Mt = (c->Npad - L.c0) / L.tile, Rt = (c->ld - L.c0) / L.tile;
+  const int B = L.B, Mt = c->Npad / L.tile, Rt = c->ld / L.tile;
   if (Mt <= 0) return;
   // fused diagonal tasks (64-tiles) pay while the launch is chain-bound; from ~4000 columns on their doubled MFMA loops are the longer chain
   // (tools/tile_probe: -8 % at 640 / 1280 columns, -5 % at 2560, +5 % at 5120, +30 % at 9216), and batched launches are throughput-bound:
@@ -215,15 +214,13 @@ static void launch_chol_dataflow(gpg_ctx* c, const CholLaunch& L) {
   const int ntask = pair ? tm->n / 2 : tm->n;              // a pair task is two task words
   const size_t per = (size_t)Mt * Rt + 1 + (L.tile == 64 ? 4 : 9) * (size_t)Mt, nflag = per * B + 8;
   // The batched 128-tile launch never takes the override (nor clears it): what the overlapped inverse follows is one tile per workgroup,
-  // which is why launch_tile128_chol keeps a single matrix away from the pair kernel while an override is waiting.  A trailing-block
-  // launch (c0 > 0) is not overlapped either: it drops a waiting override.
-  if (L.c0 > 0) c->chol_flags_override = nullptr;
+  // which is why launch_tile128_chol keeps a single matrix away from the pair kernel while an override is waiting.
   int* const fl = cleared_flags(c, nflag, !(L.tile == 128 && L.batched));
   if (!fl) return;
-  const double m = (double)(c->N - L.c0);                  // algorithmic flops: N^3 / 3 of the real matrix, not of the padded one
+  const double m = (double)c->N;                           // algorithmic flops: N^3 / 3 of the real matrix, not of the padded one
   gpg_prof_begin(c, GPG_PROF_GEMM_TRAIL, m > 0 ? B * m * m * m / 3.0 : 0.0);
   int* abort_word = fl + (size_t)Mt * Rt;
-  const TileCholArgs args{L.A, c->ld, L.c0, Mt, tm->dev, ntask, fl, abort_word + 1, abort_word, fl + (nflag - 8), L.dinv, L.info, c->N,
+  const TileCholArgs args{L.A, c->ld, /* c0: always 0 */ 0, Mt, tm->dev, ntask, fl, abort_word + 1, abort_word, fl + (nflag - 8), L.dinv, L.info, c->N,
                           L.batched ? tm->dev + tm->n : nullptr, L.a_stride, L.d_stride, L.batched ? (int)per : 0, fuse ? 1 : 0};
   if (L.tile == 128) c->last_launch_paired = pair;
   if (L.tile == 64)
@@ -235,18 +232,18 @@ static void launch_chol_dataflow(gpg_ctx* c, const CholLaunch& L) {
   gpg_prof_end(c);
 }
 
-// Factor A[c0:, c0:] (and carry the rows below the matrix) with the 64-tile kernel.
-static void launch_tile_chol(gpg_ctx* c, int c0) {
-  launch_chol_dataflow(c, CholLaunch{64, c0, 1, false, c->A, 0, c->dinv, 0, c->info});
+// The whole matrix (and the rows below it) with the 64-tile kernel.
+static void launch_tile_chol(gpg_ctx* c) {
+  launch_chol_dataflow(c, CholLaunch{64, 1, false, c->A, 0, c->dinv, 0, c->info});
 }
 // The whole matrix with the 128-tile kernels.
 static void launch_tile128_chol(gpg_ctx* c) {
   c->last_launch_paired = false;
   const bool as_batch = !c->chol_flags_override && pair128_wanted(c, 1);   // (see the override rule in launch_chol_dataflow)
-  launch_chol_dataflow(c, CholLaunch{128, 0, 1, as_batch, c->A, 0, c->dinv, 0, c->info});
+  launch_chol_dataflow(c, CholLaunch{128, 1, as_batch, c->A, 0, c->dinv, 0, c->info});
 }
 static void launch_chol_batch(gpg_ctx* c, int tile, int B, double* Abase, size_t a_stride, double* dinv_base, int d_stride, int* info_base) {
-  launch_chol_dataflow(c, CholLaunch{tile, 0, B, true, Abase, a_stride, dinv_base, d_stride, info_base});
+  launch_chol_dataflow(c, CholLaunch{tile, B, true, Abase, a_stride, dinv_base, d_stride, info_base});
 }
 
 // Minv <- -(L L^T)^-1 (lower triangle, leading dimension Npad) from finished factors, through W = L^-T (Npad x Npad): two
@@ -427,9 +424,9 @@ static bool launch_rows_fwd(gpg_ctx* c, double* W, int ldw, int rows, int valid)
 
 }  // namespace
 
-void gpg_launch_tile_chol(gpg_ctx* c, int c0) {
-  launch_tile_chol(c, c0);
-  if (c0 == 0) { c->last_factor_kernel = 1; c->last_factor_batch = 1; }
+void gpg_launch_tile_chol(gpg_ctx* c) {
+  launch_tile_chol(c);
+  c->last_factor_kernel = 1; c->last_factor_batch = 1;
 }
 void gpg_launch_tile128_chol(gpg_ctx* c) {
   launch_tile128_chol(c);
@@ -444,14 +441,13 @@ void gpg_launch_tile128_chol(gpg_ctx* c) {
 // the factorisation's flags have been cleared -- possibly BEFORE the factorisation kernel is resident -- so its grid is capped at half
 // the co-resident capacity (gpg_ctx::grid_cap): whatever the dispatch order, the factorisation finds free slots, advances, and behind
 // it the inverse.  Bounded waits apply as everywhere; a timeout here repeats the call once without the overlap (api.hip).
-static bool single_uses_tile64(const gpg_ctx* c) { return c->tail_cols > 0 && c->Npad <= c->tail_cols; }
 static size_t chol64_per(const gpg_ctx* c) {
   const size_t Mt = c->Npad / 64, Rt = c->ld / 64;
   return Mt * Rt + 1 + 4 * Mt;
 }
 // flag words of the factorisation launch that is overlapped: B matrices on 64-tiles, or ONE matrix on 128-tiles (large matrices)
 static size_t chol64_nflag(const gpg_ctx* c, int B) {
-  if (B == 1 && !single_uses_tile64(c)) {
+  if (B == 1 && !gpg_single_uses_tile64(c)) {
     const size_t Mt = c->Npad / 128, Rt = c->ld / 128;
     return flags_fill(Mt * Rt + 1 + 9 * Mt + 8);
   }
@@ -459,15 +455,15 @@ static size_t chol64_nflag(const gpg_ctx* c, int B) {
 }
 // Does a batch of B matrices go to the 128-tile factorisation kernel?  (gpg_launch_tile_chol_batch below decides with this.)
 static bool batch_uses_tile128(const gpg_ctx* c, int B) {
-  if (c->tail_cols >= (1 << 30)) return false;
-  if (c->tail_cols == 0) return true;
-  return c->Npad > c->tail_cols || (c->Npad >= 2048 && (long)B * (c->Npad / 128) >= 320);
+  if (c->factor_mode == GPG_FACTOR_TILE64) return false;
+  if (c->factor_mode != GPG_FACTOR_AUTO) return true;       // TILE128 (the blocked mode launches no batches)
+  return c->Npad > GPG_AUTO_TILE64_MAX_COLS || (c->Npad >= 2048 && (long)B * (c->Npad / 128) >= 320);
 }
 bool gpg_overlap_inverse_begin(gpg_ctx* c, int B) {
   const bool small_inv = c->inv_tile64_cols > 0 && c->Npad <= c->inv_tile64_cols;   // W on 64-tiles; above (one matrix only): on 128-tiles
   // the factorisation must be one of the dataflow launches that take the flag override: B matrices on 64-tiles, one on 64- or 128-tiles
   // (the 64-tile W reads 64-tile flags: it needs the 64-tile factorisation; the 128-tile W takes either)
-  const bool chol_ok = B > 1 ? !batch_uses_tile128(c, B) : (single_uses_tile64(c) || (c->chol_impl == 1 && !small_inv));
+  const bool chol_ok = B > 1 ? !batch_uses_tile128(c, B) : (gpg_single_uses_tile64(c) || (gpg_single_uses_tile128(c) && !small_inv));
   if (!c->overlap_inverse || B < 1 || (!small_inv && B > 1) || !chol_ok || c->prof_mask != 0 || c->stream_inv == c->stream || !c->stream_inv)
     return false;
   const size_t Mt64 = c->Npad / 64;
@@ -494,7 +490,7 @@ bool gpg_overlap_inverse_trinv(gpg_ctx* c, int B, const double* Abase, size_t a_
   // (last argument: per-matrix stride of the factorisation's flags for the batched 64-tile W; for the 128-tile W of one matrix the number of
   // 64-tile columns of the factorisation, 0 when it ran on 128-tiles itself)
   const bool small_inv = c->inv_tile64_cols > 0 && c->Npad <= c->inv_tile64_cols;
-  const int lf = small_inv ? (int)chol64_per(c) : (single_uses_tile64(c) ? c->Npad / 64 : 0);
+  const int lf = small_inv ? (int)chol64_per(c) : (gpg_single_uses_tile64(c) ? c->Npad / 64 : 0);
   const bool ok = launch_tile128_inverse_batch(c, B, Abase, a_stride, dinv_base, d_stride, Wbase, nullptr, info_base, 1,
                                                c->keep_flags + chol64_nflag(c, B), c->keep_flags, lf);
   (void)hipEventRecord(c->ev_trinv, c->stream_inv);

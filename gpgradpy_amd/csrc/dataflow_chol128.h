@@ -9,7 +9,7 @@ namespace {
 // tile128_chol_kernel: the whole factorisation as ONE dataflow launch over 128 x 128 tiles (left-looking).
 // Workgroup b owns tile (i, j) = tasks[b], column-major task order, rows i >= j (the right-hand-side rows
 // below the matrix are one more tile row):
-//     acc  = A_ij - sum_{k<j} L_ik L_jk^T   the direct-fragment MFMA loop of gemm_direct_kernel over every finished tile
+//     acc  = A_ij - sum_{k<j} L_ik L_jk^T   a direct-fragment MFMA loop (operands straight from global) over every finished tile
 //                                          column, consumed in runs as the flags come up.  The C tile is read
 //                                          once and written once per factorisation (the right-looking update
 //                                          streams it once per panel) and there is no launch chain at all.

@@ -66,7 +66,6 @@ struct gpg_ctx {
   hipStream_t stream_upd = nullptr;  // high-priority stream: look-ahead factorisation of the next diagonal block (blocked schedule)
   hipStream_t stream_inv = nullptr;  // LOWEST-priority stream: the overlapped inverse W = L^-T, which waits for the factorisation on `stream`
   int lookahead = 1;
-  int gemm_impl = 1;                 // 1: LDS-DMA ring kernel for the 128x128 updates, 0: register-staged kernel (A/B runs)
   std::vector<hipEvent_t> ev_panel, ev_upd;
   std::map<TaskListKey, TileMap> tilemaps;   // task / live-tile lists on the device, per shape (kept for the context's lifetime)
   int n = 0, d = 0, use_grad = 0, kernel = 0;
@@ -74,15 +73,14 @@ struct gpg_ctx {
   int ng = 0;                // gradient points in use (KernelSqExp.py:349-377: bvec_use_grad)
   int* gpos = nullptr;       // device [n]
   size_t A_elems = 0;        // allocated size of A (doubles), sized for all gradients
-  int panel_impl = 1;                // 1: fused panel_solve_kernel for B_p, 0: trsm64 + small gemm launches (A/B runs)
   int nb_outer = 256;   // panel width
   bool launch_error = false;  // a launch helper could not allocate its scratch / task list: nothing was launched (checked by the API call)
   int factor_fallbacks = 0;   // times a dataflow launch timed out and the call was repeated with the blocked schedule
   int last_factor_kernel = 0; // schedule of the most recent factorisation launch: 0 blocked, 1 64-tile, 2 128-tile dataflow, 3 128-tile pairs
   bool last_launch_paired = false;
   int last_factor_batch = 0;  // matrices it factorised
-  int chol_impl = 0;    // 1: whole factorisation by the 128-tile dataflow kernel
-  int tail_cols = 0;    // trailing block of at most this many columns goes to the dataflow tile kernel (0: off)
+  gpg_factor_mode factor_mode = GPG_FACTOR_AUTO;   // factorisation schedule (gpg_set_factor_mode; with_fallback sets BLOCKED); read through the
+                                                   // gpg_factor_dataflow / gpg_single_uses_tile64 / gpg_single_uses_tile128 predicates below
   int rows_max_tasks = 1 << 15;  // dataflow row solves (posterior at many points): at most this many 64 x 64 tile tasks per launch; beyond, the
                                  // blocked forward sweep is as fast (cfg3: ~5000 points; tools/post_many.py; env GPG_ROWS_MAX_TASKS overrides)
   int inv_tile64_cols = 4096;   // explicit inverse: W = L^-T on 64 x 64 tiles up to this many padded columns (0: always 128-tiles)
@@ -115,8 +113,6 @@ struct gpg_ctx {
   int max_workgroups = 0;      // > 0: cap on the grid of every persistent launch (gpg_set_max_workgroups; 0 = co-resident capacity)
   std::map<const void*, int> occupancy;   // workgroups per compute unit of each persistent kernel (occupancy query, cached)
   size_t tile_flags_cap = 0;
-  int nb_big = 0;       // wide-panel width used while at least big_rows columns remain (0: off)
-  int big_rows = 0;
   // device buffers
   double* A = nullptr;       // [ld x Npad] column-major; lower triangle + RHS rows
   double* Xt = nullptr;      // [d x n]   (coordinate-major copy of x for coalesced loads)
@@ -219,12 +215,23 @@ void gpg_launch_prep_assembly_batch(gpg_ctx* c, const AsmParams& p, int B, const
 void gpg_launch_lkd_reduce_batch(gpg_ctx* c, int slot0, int B, size_t v_stride, size_t a_stride, const int* info0 /* B words */);
 void gpg_launch_cross(gpg_ctx* c, const AsmParams& p, int nx, int nxp);   // Wt <- P^-1 Kyx (transposed)
 void gpg_launch_abs_rowsum(gpg_ctx* c, double scale, double* out_dev);    // out[i] = scale * sum_j |M_ij|, M symmetric, lower triangle in A
-void gpg_launch_tile_chol(gpg_ctx* c, int c0);                          // dataflow factorisation of A[c0:, c0:], 64-tiles
+void gpg_launch_tile_chol(gpg_ctx* c);                                  // dataflow factorisation of the matrix in A, 64-tiles
 void gpg_launch_tile128_chol(gpg_ctx* c);
 // dataflow W <- W L^-T / Z <- Z L^-1 for a few 64-row tiles; rows >= valid must be zero (their substitution is skipped);
 // false: not applicable (caller falls back on the blocked sweep)
+// ---- the factorisation schedule, read off gpg_ctx::factor_mode ----------------------------------
+// GPG_FACTOR_AUTO: ONE matrix of up to this many padded columns goes to the 64-tile kernel (shorter dependency chain), larger ones to the
+// 128-tile kernel (measured, profiles/r01_tile_probe.log); gpg_lkd_grad judges everything at one synchronisation up to the same size
+constexpr int GPG_AUTO_TILE64_MAX_COLS = 12288;
+// factorisation by one dataflow launch?  (else the blocked schedule of cholesky.hip)
+static inline bool gpg_factor_dataflow(const gpg_ctx* c) { return c->factor_mode != GPG_FACTOR_BLOCKED; }
+// a single matrix goes to the 64-tile kernel / to the 128-tile kernel (gpg_cholesky asks in this order)
+static inline bool gpg_single_uses_tile64(const gpg_ctx* c) {
+  return c->factor_mode == GPG_FACTOR_TILE64 || (c->factor_mode == GPG_FACTOR_AUTO && c->Npad <= GPG_AUTO_TILE64_MAX_COLS);
+}
+static inline bool gpg_single_uses_tile128(const gpg_ctx* c) { return gpg_factor_dataflow(c) && !gpg_single_uses_tile64(c); }
 // triangular solves as dataflow launches?  (off with the blocked factor mode, and after one of them timed out: api.hip with_fallback)
-static inline bool gpg_dataflow_solves(const gpg_ctx* c) { return c->solve_dataflow != 0 && (c->chol_impl != 0 || c->tail_cols != 0); }
+static inline bool gpg_dataflow_solves(const gpg_ctx* c) { return c->solve_dataflow != 0 && gpg_factor_dataflow(c); }
 bool gpg_overlap_inverse_begin(gpg_ctx* c, int B);          // eligible? then the next (batched) factorisation keeps its flags (call before enqueueing it)
 bool gpg_overlap_inverse_trinv(gpg_ctx* c, int B, const double* Abase, size_t a_stride, const double* dinv_base, int d_stride, double* Wbase,
                                int* info_base);             // after the factorisation was enqueued: W = L^-T on the second stream

@@ -1524,6 +1524,7 @@ class GaussianProcess(HparaOptz):
             raise _lib.GpgError(f'gpg_set_panel failed ({rc}): {self._err()}')
 
     def set_lookahead(self, on):
+        """Two-stream look-ahead of the blocked schedule on (1, default) or off (0); only bit 0 is read (include/gpgrad.h: gpg_set_lookahead)."""
         self._lib.gpg_set_lookahead(self._ctx, int(on))
 
     FACTOR_MODES = {'auto': 0, 'blocked': 1, 'tile64': 2, 'tile128': 3}

@@ -403,7 +403,8 @@ enum {
   GPG_PROF_ASSEMBLY = 0,   /* fused kernel build: algorithmic bytes 8 N (N+1) / 2                   */
   GPG_PROF_POTRF = 1,      /* diagonal-block factorisations                                         */
   GPG_PROF_TRSM = 2,       /* panel triangular solves                                               */
-  GPG_PROF_GEMM_PANEL = 3, /* updates inside a panel                                                */
+  GPG_PROF_GEMM_PANEL = 3, /* kept for the layout of the arrays below (GPG_PROF_NCAT): always reads zero,
+                            * the panel solve is one fused launch counted under GPG_PROF_TRSM          */
   GPG_PROF_GEMM_TRAIL = 4, /* fp64 MFMA factorisation kernel (dataflow Cholesky launch, or the trailing
                             * update of the blocked schedule): algorithmic flops                      */
   GPG_PROF_REDUCE = 5,     /* log-det / GLS reductions                                              */
@@ -419,15 +420,15 @@ int gpg_prof_read(gpg_ctx* ctx, double ms[GPG_PROF_NCAT], long long count[GPG_PR
 /* Tuning knobs (defaults are the measured best): panel width (multiple of 128 in [128, 1024]). */
 int gpg_set_panel(gpg_ctx* ctx, int nb_outer);
 /* bit 0 = 1 (default): look-ahead Cholesky (the next diagonal block is factorised on a second,
- * high-priority stream under the trailing update); 0: single stream.  bit 1 = 1: register-staged
- * 128x128 update kernel instead of the LDS-DMA one (A/B measurements only). */
+ * high-priority stream under the trailing update); 0: single stream.  Only bit 0 is read: bits 1 and 2
+ * selected kernel variants that no longer exist and are accepted and ignored. */
 int gpg_set_lookahead(gpg_ctx* ctx, int on);
 
 /* Factorisation schedule.  GPG_FACTOR_AUTO (default): one dataflow launch -- the 64 x 64-tile kernel up to
  * 12288 padded columns, the 128 x 128-tile kernel above (batched launches of gpg_lkd_batch switch to the 128-tile
  * kernel much earlier, see gpg_set_batch).  GPG_FACTOR_BLOCKED: right-looking blocked
- * algorithm (panel solve + trailing update per panel, look-ahead on a second stream; A/B measurements and
- * the reference point for the parity tests).  GPG_FACTOR_TILE64 / GPG_FACTOR_TILE128 force one kernel. */
+ * algorithm (panel solve + trailing update per panel, look-ahead on a second stream; the fallback after a
+ * timed-out dataflow launch and the reference point for the parity tests).  GPG_FACTOR_TILE64 / GPG_FACTOR_TILE128 force one kernel. */
 enum gpg_factor_mode { GPG_FACTOR_AUTO = 0, GPG_FACTOR_BLOCKED = 1, GPG_FACTOR_TILE64 = 2, GPG_FACTOR_TILE128 = 3 };
 int gpg_set_factor_mode(gpg_ctx* ctx, int mode);
 /* Two dataflow launches sharing one device (two processes / contexts on the same GPU) can starve each other: every

@@ -204,6 +204,52 @@ def test_failing_pivot_index(m, sched):
     assert GP.factor_fallbacks() == 0
 
 
+ROUTING_N = 2048      # gradient-free: 2048 padded columns, where GPG_FACTOR_AUTO sends 20 matrices per launch to 128-tiles and 19 to 64-tiles
+# steps of (factor mode, restart rows of calc_lkd_batch, last_factor() afterwards).  The tuples are what the build before the
+# schedule became one field (commit 5783a75) returned for the same calls on the device; they are not derived from this build.
+ROUTING = {
+    "auto_19_rows":      (("auto", 19, ("tile64", 19)),),
+    "auto_20_rows":      (("auto", 20, ("pair128", 20)),),
+    "tile64_20_rows":    (("tile64", 20, ("tile64", 20)),),
+    "tile128_19_rows":   (("tile128", 19, ("pair128", 19)),),
+    "blocked_then_auto": (("blocked", 2, ("blocked", 1)), ("auto", 1, ("tile64", 1)), ("auto", 20, ("pair128", 20))),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def _gp_routing():
+    import gpgradpy_amd
+    from oracle import gp_oracle as orc
+    X, f, _ = orc.synthetic_design(ROUTING_N, 2, seed=31)
+    GP = gpgradpy_amd.GaussianProcess(2, False, "SqExp", "base")
+    GP.set_data(X, f, np.zeros(ROUTING_N))
+    assert GP.n_data == ROUTING_N
+    GP._etaK = GP._eta_Kgrad = fc.BASE_ETA
+    return GP
+
+
+@pytest.mark.parametrize("steps", list(ROUTING))
+def test_factor_mode_routing(steps):
+    """Which kernel a factor mode sends one matrix and a batch of restart rows to, at the size where the batch rule of
+    GPG_FACTOR_AUTO switches tile size (B Npad / 128 >= 320 at Npad = 2048: 20 rows), with both forced modes on the other
+    side of that rule, and the blocked mode (one matrix per launch) handing back to the dataflow route."""
+    GP = _gp_routing()
+    GP.set_fuse_max_tiles(48)
+    GP.set_task_order(-1)
+    assert GP._lib.gpg_set_pair_mode(GP._ctx, 2) == 0
+    GP.set_max_workgroups(0)
+    GP.set_batch(-1)
+    try:
+        for mode, rows, expect in ROUTING[steps]:
+            GP.set_factor_mode(mode)
+            ln = GP.calc_lkd_batch(np.random.default_rng(32).uniform(1.0, 1.7, (rows, 2)))   # theta in [10, 50]
+            assert np.all(np.isfinite(ln))
+            assert GP.last_factor() == expect, (mode, rows, GP.last_factor())
+            assert GP.factor_fallbacks() == 0
+    finally:
+        GP.set_factor_mode("auto")
+
+
 def test_setters_check_their_arguments():
     GP = _gp("sqexp_n65")
     lib, ctx = GP._lib, GP._ctx

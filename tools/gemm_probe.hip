@@ -7,9 +7,8 @@ void gpg_prof_begin(gpg_ctx*, int, double) {}
 void gpg_prof_end(gpg_ctx*) {}
 void gpg_launch_identity(gpg_ctx*, double*, int) {}
 int main(int argc, char** argv) {
-  int Nt = argc > 1 ? atoi(argv[1]) : 16384, K = argc > 2 ? atoi(argv[2]) : 256, impl = argc > 3 ? atoi(argv[3]) : 1;
+  int Nt = argc > 1 ? atoi(argv[1]) : 16384, K = argc > 2 ? atoi(argv[2]) : 256;
   gpg_ctx c;
-  c.gemm_impl = impl;
   hipStreamCreate(&c.stream);
   int ld = Nt + 128;
   double *C, *P;
@@ -71,6 +70,6 @@ int main(int argc, char** argv) {
            sum[0] / nw / (K / 8), sum[1] / nw / (K / 8), sum[2] / nw, sum[3] / nw * 0.01, (sum[2] / nw) / (sum[3] / nw * 10.0));
   }
 #endif
-  printf("Nt=%d K=%d impl=%d: %.3f ms/launch, %.2f TFLOP/s (algorithmic, lower triangle)\n", Nt, K, impl, ms / reps, fl / ms * 1e-9);
+  printf("Nt=%d K=%d: %.3f ms/launch, %.2f TFLOP/s (algorithmic, lower triangle)\n", Nt, K, ms / reps, fl / ms * 1e-9);
   return 0;
 }

@@ -8,9 +8,8 @@ void gpg_prof_begin(gpg_ctx*, int, double) {}
 void gpg_prof_end(gpg_ctx*) {}
 void gpg_launch_identity(gpg_ctx*, double*, int) {}
 int main(int argc, char** argv) {
-  int rows = argc > 1 ? atoi(argv[1]) : 16384, nb = argc > 2 ? atoi(argv[2]) : 512, impl = argc > 3 ? atoi(argv[3]) : 1;
+  int rows = argc > 1 ? atoi(argv[1]) : 16384, nb = argc > 2 ? atoi(argv[2]) : 512;
   gpg_ctx c;
-  c.panel_impl = impl;
   hipStreamCreate(&c.stream);
   const int ld = rows + nb;
   c.ld = ld; c.Npad = nb; c.N = nb;
@@ -50,7 +49,7 @@ int main(int argc, char** argv) {
            sum[0] / nw, sum[1] / nw, sum[2] / nw, sum[3] / nw, sum[4] / nw);
   }
 #endif
-  printf("rows=%d nb=%d impl=%d: %.1f us/panel, %.2f TFLOP/s (rows nb^2)\n", rows, nb, impl, ms / reps * 1e3,
+  printf("rows=%d nb=%d: %.1f us/panel, %.2f TFLOP/s (rows nb^2)\n", rows, nb, ms / reps * 1e3,
          (double)rows * nb * nb * reps / ms * 1e-9);
   return 0;
 }

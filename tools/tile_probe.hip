@@ -28,7 +28,7 @@ int main(int argc, char** argv) {
   hipStreamCreate(&c.stream);
   c.stream_upd = c.stream; c.lookahead = 0;
   c.Npad = n; c.N = n; c.ld = n + 128; c.nb_outer = 512;
-  c.chol_impl = impl == 1; c.tail_cols = impl == 2 ? n : 0;
+  c.factor_mode = impl == 1 ? GPG_FACTOR_TILE128 : impl == 2 ? GPG_FACTOR_TILE64 : GPG_FACTOR_BLOCKED;
   if (getenv("GPG_PROBE_MAX_WG")) c.max_workgroups = atoi(getenv("GPG_PROBE_MAX_WG"));   // cap on the persistent grid (e.g. 256 = one workgroup per CU)
   c.num_cus = 256;
   if (getenv("GPG_PROBE_ORDER")) c.task_order = atoi(getenv("GPG_PROBE_ORDER"));
@@ -49,7 +49,7 @@ int main(int argc, char** argv) {
   const size_t total = (size_t)c.ld * n;
   const int B = (impl == 5 || impl == 6) ? (argc > 3 ? atoi(argv[3]) : 8) : 1;   // 5: batched 128-tile kernel, 6: batched 64-tile kernel
   double* bA = nullptr; double* bD = nullptr; int* binfo = nullptr;
-  if (B > 1) { hipMalloc(&bA, sizeof(double) * (size_t)c.ld * n * B); hipMalloc(&bD, sizeof(double) * (size_t)n * B); hipMalloc(&binfo, sizeof(int) * B); hipMemset(binfo, 0, sizeof(int) * B); c.chol_impl = 1; c.tail_cols = impl == 6 ? n : 0; }
+  if (B > 1) { hipMalloc(&bA, sizeof(double) * (size_t)c.ld * n * B); hipMalloc(&bD, sizeof(double) * (size_t)n * B); hipMalloc(&binfo, sizeof(int) * B); hipMemset(binfo, 0, sizeof(int) * B); c.factor_mode = impl == 6 ? GPG_FACTOR_TILE64 : GPG_FACTOR_TILE128; }
   float best = 1e30f;
   for (int rep = 0; rep < 3; ++rep) {
     if (B > 1) for (int b = 0; b < B; ++b) hipLaunchKernelGGL(fill_spd, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c.stream, bA + (size_t)b * total, c.ld, n);
