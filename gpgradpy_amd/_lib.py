@@ -25,6 +25,7 @@ ABI_SYMBOLS = (
     "gpg_multi_lkd_batch", "gpg_set_mean_order", "gpg_lkd_beta", "gpg_setup_eval_mean", "gpg_multi_set_mean_order",
     "gpg_predict_joint", "gpg_set_gram_splits", "gpg_set_mean_uncertainty", "gpg_mean_gram", "gpg_loo",
     "gpg_set_fuse_max_tiles", "gpg_set_task_order", "gpg_predict_second", "gpg_set_second_chunk",
+    "gpg_paths_setup", "gpg_paths_eval", "gpg_paths_coeff",
 )
 
 
@@ -101,6 +102,12 @@ def load():
     lib.gpg_predict_second.restype = C.c_int
     lib.gpg_set_second_chunk.argtypes = [vp, C.c_int]
     lib.gpg_set_second_chunk.restype = C.c_int
+    lib.gpg_paths_setup.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, dp, C.c_double]
+    lib.gpg_paths_setup.restype = C.c_int
+    lib.gpg_paths_eval.argtypes = [vp, C.c_int, dp, dp, dp]
+    lib.gpg_paths_eval.restype = C.c_int
+    lib.gpg_paths_coeff.argtypes = [vp, dp, dp]
+    lib.gpg_paths_coeff.restype = C.c_int
     lib.gpg_set_mean_uncertainty.argtypes = [vp, C.c_int]
     lib.gpg_set_mean_uncertainty.restype = C.c_int
     lib.gpg_mean_gram.argtypes = [vp, dp]

@@ -285,7 +285,7 @@ void gpg_destroy(gpg_ctx* c) {
                     c->ws[1].A, c->ws[1].dvec, c->ws[1].invp, c->ws[1].zvec, c->ws[1].tmpv, c->ws[1].dinv,
                     c->Xt, c->y, c->noise, c->scal, c->eval_beta_dev, c->Wt, c->xq_dev,
                     c->musig, c->gradbuf, c->dense_tmp, c->Wfull, c->Minv, c->gpartial, c->batchA, c->batchV, c->vec_rows, c->vec_x, c->apply_buf,
-                    c->batchW, c->batchM, c->batchZ, c->gres, c->Kbuf, c->Tbuf, c->jbuf, c->loo_scr};
+                    c->batchW, c->batchM, c->batchZ, c->gres, c->Kbuf, c->Tbuf, c->jbuf, c->loo_scr, c->paths_buf, c->paths_scr};
   for (double* b : bufs) if (b) (void)hipFree(b);
   gpg_meanunc_free(c);
   if (c->info) (void)hipFree(c->info);
@@ -337,7 +337,7 @@ int gpg_set_grad_mask(gpg_ctx* c, const unsigned char* use_grad_pt) {
   c->ld = c->Npad + c->R;                                        // never exceeds the allocation made for all gradients
   c->have_data = false;
   c->alpha_valid = false;
-  c->factor_valid = c->eval_ready = c->prep_valid = false;
+  c->factor_valid = c->eval_ready = c->prep_valid = c->paths_ready = false;
   c->ws[0].factor_valid = c->ws[1].factor_valid = c->ws[0].prep_valid = c->ws[1].prep_valid = false;
   if (c->dense_tmp) { (void)hipFree(c->dense_tmp); c->dense_tmp = nullptr; }
   if (c->batchA) { (void)hipFree(c->batchA); (void)hipFree(c->batchV); c->batchA = c->batchV = nullptr; c->batch_cap = 0; }
@@ -365,7 +365,7 @@ int gpg_set_data(gpg_ctx* c, const double* x, const double* data_vec, const doub
   }
   c->have_data = true;
   c->alpha_valid = false;
-  c->factor_valid = c->eval_ready = c->prep_valid = false;
+  c->factor_valid = c->eval_ready = c->prep_valid = c->paths_ready = false;
   c->ws[0].factor_valid = c->ws[1].factor_valid = c->ws[0].prep_valid = c->ws[1].prep_valid = false;
   return 0;
 }
@@ -824,7 +824,7 @@ static int gpg_setup_eval_once(gpg_ctx* c, const gpg_hp* hp, double beta, const 
   if (rc) return rc;
   GPG_HIP_OK(c, hipSetDevice(c->device));
   GPG_WS(c, 1);                                   // the posterior's own factor storage (GpEvalModel.py:17-57)
-  c->eval_ready = false;
+  c->eval_ready = c->paths_ready = false;         // sample paths (paths.hip) belong to the posterior they were drawn from
   if (betav) {
     if (!c->eval_beta_dev) GPG_HIP_OK(c, hipMalloc(&c->eval_beta_dev, sizeof(double) * GPG_BETA_STRIDE));
     GPG_HIP_OK(c, hipStreamSynchronize(c->stream));             // (a predict of the previous posterior may still read the vector)
@@ -944,7 +944,7 @@ int gpg_set_mean_order(gpg_ctx* c, int order) {
   c->n_beta = order == 1 ? c->d + 1 : 1;
   c->prep_beta = nullptr;
   c->alpha_valid = c->last_beta_valid = false;
-  c->factor_valid = c->eval_ready = c->prep_valid = false;
+  c->factor_valid = c->eval_ready = c->prep_valid = c->paths_ready = false;
   c->ws[0].factor_valid = c->ws[1].factor_valid = c->ws[0].prep_valid = c->ws[1].prep_valid = false;
   return 0;
 }

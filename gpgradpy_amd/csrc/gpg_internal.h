@@ -155,6 +155,15 @@ struct gpg_ctx {
   double *mu_cf = nullptr, *mu_cb = nullptr, *mu_q = nullptr;   // into mu_scr, set by gpg_meanunc_rows
   double* loo_scr = nullptr; // per-call scratch of gpg_loo (loo.hip): K-chunk partials | prec | cov | resid | qy | H^-1 V' alpha | bad flags
   size_t loo_scr_elems = 0;
+  // posterior sample paths (paths.hip): state of gpg_paths_setup, kept until the posterior is set up again
+  bool paths_ready = false;     // cleared by gpg_setup_eval*, gpg_set_data, gpg_set_grad_mask, gpg_set_mean_order
+  int paths_S = 0, paths_Sp = 0, paths_M = 0;   // paths, paths padded to 64, features
+  double paths_sv = 0.0;        // sqrt(varK)
+  double* paths_buf = nullptr;  // omega [M x d] | phase [M] | w^T [M x Sp] | U [Npad x Sp] | ddiag [Npad] | backward-sweep scratch [Sp x 64]
+  size_t paths_buf_elems = 0;
+  double *paths_omega = nullptr, *paths_phase = nullptr, *paths_wT = nullptr, *paths_U = nullptr, *paths_dd = nullptr, *paths_tb = nullptr;
+  double* paths_scr = nullptr;  // per-call scratch of gpg_paths_eval / gpg_paths_coeff (grown, never shrunk)
+  size_t paths_scr_bytes = 0;
   double* batchA = nullptr;     // [batch_cap x A_elems] workspaces of the batched small-matrix factorisation (on first use)
   double* batchV = nullptr;     // [batch_cap x 3 x Npad] dvec / invp / dinv of each batched matrix
   int batch_cap = 0;

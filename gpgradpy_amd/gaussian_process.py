@@ -20,6 +20,7 @@ from .hpara_optz import HparaOptz
 from .joint import draw_from_joint
 from .loo import loo_by_point, loo_by_row, point_rows
 from .second import second_from_blocks
+from .paths import PosteriorPaths, prepare_draws
 
 
 class DeviceChoFactor:
@@ -134,6 +135,7 @@ class GaussianProcess(HparaOptz):
         self._ctx_shape = None
         self.KernEta_chofac = None
         self.invKernEta_fdiff = None
+        self._paths_current = None       # the PosteriorPaths object whose draws the device holds (sample_paths)
 
     def close(self):
         """Free the device context (every workspace, factor and buffer of this model) now; the object can take new data
@@ -145,6 +147,7 @@ class GaussianProcess(HparaOptz):
             self.KernEta_chofac = None
             self.invKernEta_fdiff = None
             self._eval_ready = False
+            self._paths_current = None
 
     def __del__(self):
         try:
@@ -1201,6 +1204,7 @@ class GaussianProcess(HparaOptz):
     def setup_eval_model(self, calc_cond=False):
         """GpEvalModel.py:17-57: factor kept on the device, alpha = K^-1 (y - V beta) returned to the host."""
         self._hp_vals_model_setup = copy.copy(self.hp_vals)
+        self._paths_current = None                      # sample paths belong to the posterior they were drawn from
         hp, keep = self._make_hp(self.hp_vals, 1.0, closed_form=not self.b_has_noisy_data)   # b_normlz_w_varK=True
         beta = np.ascontiguousarray(np.ravel(self.hp_vals.beta), dtype=np.float64)
         assert beta.size == self.n_beta_coeff, \
@@ -1430,6 +1434,53 @@ class GaussianProcess(HparaOptz):
         if not calc_grad:
             return s, None
         return s[:, :nx], np.transpose(s[:, nx:].reshape(-1, self.dim, nx), (0, 2, 1))
+
+    def sample_paths(self, n_paths, n_features=4096, seed=None, omega=None, phase=None, w=None, z=None, noise_draw=True,
+                     mean_unc=False):
+        """n_paths draws from the posterior AS FUNCTIONS (pathwise conditioning on the factor kept by setup_eval_model with a
+        random-Fourier-feature prior; include/gpgrad.h: gpg_paths_setup, host side gpgradpy_amd/paths.py).  Returns a
+        PosteriorPaths object: paths(xq, calc_grad=False) gives f [S, nx] (and dfdx [S, nx, dim]) of the same S functions at any
+        points in any number of calls; paths.coeff [S, n_data] and paths.ddiag [n_data] are the coefficient vectors and the
+        diagonal (noise / varK plus nugget) of the formula.  omega [M, dim] / phase [M], w [S, M], z [S, n_data]: explicit
+        frequencies and standard normals; what is not given is drawn from np.random.default_rng(seed) (n_features frequencies by
+        the spectral law of the kernel).  noise_draw=False leaves the noise / nugget draw z out.  Paths with re-drawn mean
+        coefficients are not offered: mean_unc=True raises, as do the data-rescaling methods."""
+        assert self.KernEta_chofac is not None, 'To evaluate the surr the Cholesky decomposition is required'
+        if mean_unc:
+            raise Exception('sample_paths() is not setup for mean_unc=True: paths with re-drawn mean coefficients are out of scope')
+        if (self.hp_vals == self._hp_vals_model_setup) is False:
+            raise Exception('Cannot change hp_vals between calling setup_eval_model() and eval_model()')
+        if self.b_use_data_scl:
+            raise Exception('The method sample_paths() is not setup for cases where data must be rescaled')
+        if not self._eval_ready:
+            raise Exception('setup_eval_model() must be called (again): set_data() replaced the data of the device model')
+        hp = self.hp_vals
+        om, ph, w, z = prepare_draws(self.kernel_type, np.ravel(hp.theta), hp.kernel if self.kernel_type == 'RatQu' else None,
+                                     self.n_data, n_paths, n_features, seed, omega, phase, w, z, noise_draw)
+        self._set_mean_unc(False)
+        rc = self._lib.gpg_paths_setup(self._ctx, w.shape[0], om.shape[0], _lib.as_dp(om), _lib.as_dp(ph), _lib.as_dp(w),
+                                       None if z is None else _lib.as_dp(z), float(hp.varK))
+        if rc != 0:
+            self._paths_current = None
+            raise _lib.GpgError(f'gpg_paths_setup failed ({rc}): {self._err()}')
+        self._paths_current = PosteriorPaths(self, w.shape[0], self.dim, self.n_data, om, ph, w, z)
+        return self._paths_current
+
+    def _paths_eval(self, paths, xq, calc_grad):
+        nx, S = xq.shape[0], paths.n_paths
+        f = np.empty((S, nx))
+        dfdx = np.empty((S, nx, self.dim)) if calc_grad else None
+        rc = self._lib.gpg_paths_eval(self._ctx, nx, _lib.as_dp(xq), _lib.as_dp(f), None if dfdx is None else _lib.as_dp(dfdx))
+        if rc != 0:
+            raise _lib.GpgError(f'gpg_paths_eval failed ({rc}): {self._err()}')
+        return (f, dfdx) if calc_grad else f
+
+    def _paths_coeff(self, paths):
+        c, dd = np.empty((paths.n_paths, self.n_data)), np.empty(self.n_data)
+        rc = self._lib.gpg_paths_coeff(self._ctx, _lib.as_dp(c), _lib.as_dp(dd))
+        if rc != 0:
+            raise _lib.GpgError(f'gpg_paths_coeff failed ({rc}): {self._err()}')
+        return c, dd
 
     def loo_cv(self, mean_unc=False, by='point'):
         """Leave-one-out cross-validation of the model set up by setup_eval_model, without a refit (include/gpgrad.h: gpg_loo;

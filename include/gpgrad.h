@@ -315,6 +315,55 @@ int gpg_predict_second(gpg_ctx* ctx, int nx, const double* xq, double varK, doub
  * points < 0 and points (dim + 1) > 4096 return -1.  Chunked and unchunked results agree to rounding at least. */
 int gpg_set_second_chunk(gpg_ctx* ctx, int points);
 
+/* Posterior sample paths: functions drawn from the posterior kept by gpg_setup_eval*, by pathwise conditioning (Matheron's rule) on
+ * a random-Fourier-feature prior (the reference has no counterpart).  For path s
+ *     f_s(x) = m(x) + k(x, X) c_s + sqrt(varK) phi(x)' w_s,       c_s = alpha - sqrt(varK) Kcov^-1 (Phi_X w_s + D^(1/2) z_s),
+ * m the mean function, alpha = Kcov^-1 (y - V beta) and Kcov of gpg_setup_eval*, k(x, X) the cross-covariance rows of gpg_predict_joint,
+ * phi(x)_m = sqrt(2 / M) cos(omega_m . x + phase_m), Phi_X [N, M] its values on the value rows and d phi / d x_k on the gradient rows of
+ * the training data (row layout of gpg_set_data, gpg_set_grad_mask honoured), D [N] = diag(Kcov) - diag(Kern): noise / varK_mat plus
+ * the nugget as the well-conditioning method adds it (eta dvec for PRECON, eta for BASE), taken as the difference of the two diagonals
+ * as gpg_get_matrix(1) and (0) return them.  With omega drawn from the spectral density of the kernel (the host's business: the device
+ * never needs the law) and w, z standard normal, f_s is a draw from the posterior up to the random-feature approximation of the prior.
+ * Given (omega, phase, w, z) a path is ONE smooth function: gpg_paths_eval at any points, in any number of calls, evaluates the same
+ * function, and dfdx is its exact gradient.
+ * Cost: the set-up is the feature rows of the training data plus one forward and one backward multi-row sweep of S rows through the kept
+ * factor, O(S N^2), no factorisation; an evaluation is the cross rows plus an [nx (dim + 1)] x N x S product on fp64 MFMA and the feature
+ * rows of the query points: no sweep, no N^2 work, no row cap (the host loops over chunks of points as gpg_predict_second does,
+ * gpg_set_second_chunk applies), one device-to-host copy per output and one synchronisation per call.  The mean part m(x) + k(x, X) alpha
+ * is summed with compensation by the kernels of gpg_predict_joint and is the same bits as its `mean`; the deviation is a split-K sum
+ * with min(N_pad / 64, 64) K-chunks (gpg_set_gram_splits overrides) added in chunk order, the features are added in one fixed order.
+ * Ordinary grids, no atomics: the same bits from run to run, under any gpg_set_max_workgroups, and whichever other points share the call.
+ * Likelihood-side state is neither read nor invalidated.
+ * The automatic chunk of gpg_paths_eval holds 4096 / (S_pad / 64) rows (at least 256), a function of S and dim only, so the split-K
+ * partials stay within 128 MB for any S.
+ * Registers (-Rpass-analysis=kernel-resource-usage, gfx950; VGPRs / scratch bytes / waves per SIMD): rows_coeff_splitk_kernel
+ * 50 / 0 / 5; feature_rows_kernel d = 1: 60 / 0 / 8, d = 4: 64 / 0 / 8, d = 8: 77 / 0 / 6, d = 16: 131 / 0 / 3; paths_finish_kernel
+ * 40 / 0 / 8.  No kernel of paths.hip uses scratch.
+ * Measured on one MI355X (tools/paths_time.py, S = 64, M = 4096; n = 2000, d = 8 | n = 500, d = 4; the full table is in README.md,
+ * "Posterior sample paths"):
+ *   gpg_paths_setup 11.2 | 2.6 ms = feature kernel 0.77 | 0.46 ms + two sweeps 6.45 | 0.89 ms + host transposition, uploads, launches;
+ *   gpg_paths_eval with gradients at nx = 64: 0.57 | 0.43 ms = cross rows 18 | 8 us + product kernel 46 | 11 us (29.0 | 9.6 TFLOP/s,
+ *   Wt read at 1.8 | 0.6 TB/s) + feature kernel 368 | 327 us + mean, finishing kernel, copies; at nx = 448: 1.22 | 0.55 ms (product
+ *   kernel 228 | 25 us: 40.8 | 29.2 TFLOP/s, 2.6 | 1.9 TB/s; feature kernel 484 | 345 us);
+ *   for scale, same points, same build: gpg_predict_grad 6.54 | 0.95 ms (nx = 64), 8.81 | 1.04 ms (nx = 448); gpg_predict_joint
+ *   5.03 | 0.61 ms and 35.6 | 1.70 ms.
+ * An evaluation pays no sweep (11x below gpg_predict_grad at N = 18000), but it is not "about the cost of the cross rows": two thirds
+ * of it is the feature kernel on the query rows (one workgroup per point over all M features). */
+
+/* S paths on the posterior kept by gpg_setup_eval*.  omega [M, dim] row-major, phase [M], w [S, M], z [S, N] (NULL = zeros:
+ * no noise/nugget draw), all host.  1 <= S <= 1024, 1 <= M <= 65536, varK >= 0 (what gpg_predict* take as varK).  -1 with a message
+ * before a successful gpg_setup_eval*, for arguments out of range, and with gpg_set_mean_uncertainty on (paths with re-drawn mean
+ * coefficients are out of scope); -2 out of memory. */
+int gpg_paths_setup(gpg_ctx* ctx, int n_paths, int n_feat, const double* omega, const double* phase,
+                    const double* w, const double* z, double varK);
+/* f [S, nx]; dfdx [S, nx, dim] (NULL = not computed, and then no derivative rows are built).  Any nx >= 1.  -1 with a message when no
+ * paths are set up, or when gpg_setup_eval*, gpg_set_data, gpg_set_grad_mask or gpg_set_mean_order ran since gpg_paths_setup: the paths
+ * belong to that posterior. */
+int gpg_paths_eval(gpg_ctx* ctx, int nx, const double* xq, double* f, double* dfdx);
+/* c [S, N] (the coefficient vectors above) and, if not NULL, ddiag [N] = the diagonal D that was used (either may be NULL, not both).
+ * Errors as gpg_paths_eval. */
+int gpg_paths_coeff(gpg_ctx* ctx, double* c, double* ddiag);
+
 /* Materialisation on request (the 7-tuple of Kernel.py:307 carries N x N arrays; the fast path never
  * copies them).  out is [N, N] column-major == row-major (symmetric) for which = 0..2:
  *   0 Kern (Kernel.py:213-216), 1 Kcov (Kernel.py:237 / 277), 2 the matrix that is factorised
